@@ -15,15 +15,21 @@ tree replicated on every GPU, queries independent (no data-path collective).  De
 ``--scaling strong`` = BASELINE configs[3] literally: ONE 7.2 M batch cut into N contiguous
 shards, rank 0 collecting every rank's (index, distance) rows with one RCCL gather per step,
 issued asynchronously so that it overlaps the next step's search (all gathers complete inside the
-timed region); ``value`` is that.  The same run then times the weak form (every rank searches a
+timed region); ``value`` is that.  With ``--full`` the same run then times the weak form (every rank searches a
 full 7.2 M batch of its own: same cloud, another seed) and reports it as the extra object
 ``"weak"``.  ``--scaling weak`` makes the weak form ``value`` instead.
 
-At N = 1 the line also carries (none of it inside the timed region of ``value``):
-``host_buffers`` (the host-pointer entry ``ptk_search_knn`` on pageable arrays: H2D + search +
-D2H), ``also`` (the same search on Morton-ordered queries and on cloud U), ``config3`` (knn = 16
-and the radius search of BASELINE configs[2] with their own roofline figures), ``pipelined``
-(two batches in flight on two HIP streams).
+A plain run sets up, warms up, times the steps and prints the headline.  Everything else is
+measured with ``--full`` only: the parity sample against the oracle, the roofline figures, the
+CPU baseline, the other scaling form (N > 1) and, at N = 1 (none of it inside the timed region
+of ``value``): ``host_buffers`` (the host-pointer entry ``ptk_search_knn`` on pageable arrays:
+H2D + search + D2H), ``also`` (the same search on Morton-ordered queries and on cloud U),
+``config3`` (knn = 16 and the radius search of BASELINE configs[2] with their own roofline
+figures), ``pipelined`` (two batches in flight on two HIP streams).
+
+``--dump-outputs DIR`` writes what the last timed step returned, for a fixed seeded sample of
+its rows: ``DIR/index.npy`` (float64), ``DIR/distance.npy`` (float32), both ``(rows, k)``, and
+``DIR/rows.npy`` (float64, the query row of each).
 
 Rank 0 prints ONE JSON line; see README.md / DESIGN.md for the field meanings.
 """
@@ -79,15 +85,20 @@ def parse_args():
     ap.add_argument("--reorder", choices=["auto", "on", "off"], default="auto")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="N > 1: which form is `value`: strong = one batch cut into N shards (BASELINE configs[3]), "
-                         "weak = a full batch per GPU; the other one is reported as an extra object")
+                         "weak = a full batch per GPU; with --full the other one is reported as an extra object")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: parity sample, roofline, CPU "
+                         "baseline, pipelined, the other scaling form and the extras (each --no-* below drops one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed seeded sample of the last timed step's rows to DIR/*.npy")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1: skip host_buffers / also / config3 (the headline line only)")
+                    help="with --full, N = 1: skip host_buffers / also / config3")
     ap.add_argument("--streams", type=int, default=1,
                     help="HIP streams successive steps are issued on round-robin (single GPU only).  1 (default): one "
                          "batch at a time, the per-kernel durations are those of an isolated call.  > 1: batches "
                          "overlap (the handle keeps one scratch block per stream); kernel_ms then covers "
                          "kernels that shared the GPU")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the two-streams context measurement")
+    ap.add_argument("--no-pipelined", action="store_true", help="with --full: skip the two-streams context measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--single-process-worker", type=int, default=0, help=argparse.SUPPRESS)
@@ -829,6 +840,30 @@ def run_single_process_form(args, ndev, timeout_s=240):
         return {"devices": ndev, "error": repr(exc)[:400]}
 
 
+#: --dump-outputs: at most this many (index, distance) entries are written (12 bytes each + 8 per row), and the rows
+#: are drawn with this seed, so that two builds given the same arguments write the same rows.
+DUMP_ENTRIES = 2_000_000
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, rows, k):
+    """Writes a fixed seeded sample of ``rows`` (the int32 ``(nq, k, 2)`` result of a timed step) as
+    ``index.npy`` (float64), ``distance.npy`` (float32) and ``rows.npy`` (float64, the sampled query rows)."""
+    import torch
+
+    import pico_tree_amd as pt
+
+    total = int(rows.shape[0])
+    keep = min(total, max(1, DUMP_ENTRIES // k))
+    sel = np.arange(total) if keep == total else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=keep, replace=False))
+    got = pt.DeviceNeighbors(rows[torch.from_numpy(sel).to(rows.device)]).numpy().reshape(keep, k)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "index.npy"), got["index"].astype(np.float64))
+    np.save(os.path.join(out_dir, "distance.npy"), np.ascontiguousarray(got["distance"], dtype=np.float32))
+    np.save(os.path.join(out_dir, "rows.npy"), sel.astype(np.float64))
+
+
 def main():
     args = parse_args()
     if args.cpu_baseline_worker:
@@ -954,7 +989,7 @@ def main():
 
     main_is_weak = args.scaling == "weak" and world > 1
     form = run_form(main_is_weak)
-    other = run_form(not main_is_weak) if world > 1 else None
+    other = run_form(not main_is_weak) if world > 1 and args.full else None
     weak = form["weak"]
     per, lo, hi, out, dq, sharded, prof = (form[x] for x in ("per", "lo", "hi", "out", "dq", "sharded", "prof"))
     total_queries, n_streams = form["total"], form["n_streams"]
@@ -963,7 +998,7 @@ def main():
     # Context, never `value`: the same batches with two in flight on two HIP streams of the same handle
     # ("Pipelined batches").  Single GPU, default stream count only.
     pipelined = None
-    if world == 1 and n_streams == 1 and not args.no_pipelined:
+    if args.full and world == 1 and n_streams == 1 and not args.no_pipelined:
         two = [torch.cuda.Stream(device=dev) for _ in range(2)]
         outs2 = [torch.empty((per, k, 2), dtype=torch.int32, device=dev) for _ in range(2)]
 
@@ -983,168 +1018,172 @@ def main():
 
     result = None
     if rank == 0:
-        import oracle
+        if args.dump_outputs:  # what the caller of the timed path received from its last step
+            dump_outputs(args.dump_outputs,
+                         out[:hi - lo] if world == 1 else sharded.result(rows_per_rank=per if weak else None), k)
+        parity_ok, roofline, extras, cpu = None, None, {}, None
+        if args.full:
+            import oracle
 
-        # Sanity: the timed output equals the oracle on a sample (never timed).
-        res = pt.DeviceNeighbors(out).numpy()
-        sample = np.linspace(0, (hi - lo) - 1, num=min(4096, hi - lo), dtype=np.int64)
-        ref_small = oracle.Oracle(pts, args.leaf, "port")
-        want = ref_small.search_knn(q[lo:hi][sample], k)
-        got = res[sample] if k > 1 else res[sample][:, None]
-        parity_ok = bool(got.tobytes() == want.tobytes())
-        if world > 1:  # and the rows rank 0 gathered from rank 1 (last step)
-            rows = sharded.result(rows_per_rank=per if weak else None)
-            if weak:
-                q1 = own_batch(1)
-                got1 = pt.DeviceNeighbors(rows[per:2 * per]).numpy()[sample]
-                want1 = ref_small.search_knn(q1[sample], k)
-            else:
-                sh1 = shard_of(nq, world, 1)
-                s1 = np.linspace(sh1.lo, sh1.hi - 1, num=min(4096, sh1.rows), dtype=np.int64)
-                got1 = pt.DeviceNeighbors(rows).numpy()[s1]
-                want1 = ref_small.search_knn(q[s1], k)
-            got1 = got1 if k > 1 else got1[:, None]
-            parity_ok = parity_ok and bool(got1.tobytes() == want1.tobytes())
+            # Sanity: the timed output equals the oracle on a sample (never timed).
+            res = pt.DeviceNeighbors(out).numpy()
+            sample = np.linspace(0, (hi - lo) - 1, num=min(4096, hi - lo), dtype=np.int64)
+            ref_small = oracle.Oracle(pts, args.leaf, "port")
+            want = ref_small.search_knn(q[lo:hi][sample], k)
+            got = res[sample] if k > 1 else res[sample][:, None]
+            parity_ok = bool(got.tobytes() == want.tobytes())
+            if world > 1:  # and the rows rank 0 gathered from rank 1 (last step)
+                rows = sharded.result(rows_per_rank=per if weak else None)
+                if weak:
+                    q1 = own_batch(1)
+                    got1 = pt.DeviceNeighbors(rows[per:2 * per]).numpy()[sample]
+                    want1 = ref_small.search_knn(q1[sample], k)
+                else:
+                    sh1 = shard_of(nq, world, 1)
+                    s1 = np.linspace(sh1.lo, sh1.hi - 1, num=min(4096, sh1.rows), dtype=np.int64)
+                    got1 = pt.DeviceNeighbors(rows).numpy()[s1]
+                    want1 = ref_small.search_knn(q[s1], k)
+                got1 = got1 if k > 1 else got1[:, None]
+                parity_ok = parity_ok and bool(got1.tobytes() == want1.tobytes())
 
-        rng = np.random.default_rng(7)
-        cs = rng.choice(nq, size=min(args.counter_sample, nq), replace=False)
-        b_per_q, visits = algorithmic_bytes(ref_small, q[np.sort(cs)], k, dim)
-        ref_small.close()
+            rng = np.random.default_rng(7)
+            cs = rng.choice(nq, size=min(args.counter_sample, nq), replace=False)
+            b_per_q, visits = algorithmic_bytes(ref_small, q[np.sort(cs)], k, dim)
+            ref_small.close()
 
-        launches = max(int(prof["launches"]), 1)
-        kernel_ms = prof["search_ms"] / launches
-        q_per_launch = prof["queries"] / launches if prof["launches"] else per
-        achieved = (b_per_q * q_per_launch) / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
-        traffic, traffic_src = (None, None)
-        if k == 1 and not args.n and not args.nq and args.cloud == "L" and world == 1:
-            traffic, traffic_src = measured_traffic(TRAVERSAL_KERNELS)
-        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBS, 5),
-                    "traffic": None if traffic is None else round(traffic / 1e9, 3),
-                    "traffic_unit": "GB per launch (2 x FETCH_SIZE + WRITE_SIZE, rocprofv3 --pmc)",
-                    "traffic_static": True,  # counters cannot be read inside the process: per-launch figure of the
-                    "traffic_source": traffic_src,  # committed rocprofv3 --pmc passes of this same command (that file)
-                    "algorithmic_gb_per_launch": round(b_per_q * q_per_launch / 1e9, 3),
-                    "kernel": " + ".join(TRAVERSAL_KERNEL_NAMES) if k == 1 else "ptk::knn_reg_kernel / ptk::knn_kernel",
-                    "kernel_ms": round(kernel_ms, 4), "reorder_ms": round(prof["reorder_ms"] / launches, 4),
-                    "other_ms": round(prof["other_ms"] / launches, 4),
-                    "bytes_per_query": round(b_per_q, 1), "queries_per_launch": int(q_per_launch),
-                    "visits_per_query": {kk: round(v, 2) for kk, v in visits.items()}}
+            launches = max(int(prof["launches"]), 1)
+            kernel_ms = prof["search_ms"] / launches
+            q_per_launch = prof["queries"] / launches if prof["launches"] else per
+            achieved = (b_per_q * q_per_launch) / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0
+            traffic, traffic_src = (None, None)
+            if k == 1 and not args.n and not args.nq and args.cloud == "L" and world == 1:
+                traffic, traffic_src = measured_traffic(TRAVERSAL_KERNELS)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBS, 5),
+                        "traffic": None if traffic is None else round(traffic / 1e9, 3),
+                        "traffic_unit": "GB per launch (2 x FETCH_SIZE + WRITE_SIZE, rocprofv3 --pmc)",
+                        "traffic_static": True,  # counters cannot be read inside the process: per-launch figure of the
+                        "traffic_source": traffic_src,  # committed rocprofv3 --pmc passes of this same command (that file)
+                        "algorithmic_gb_per_launch": round(b_per_q * q_per_launch / 1e9, 3),
+                        "kernel": " + ".join(TRAVERSAL_KERNEL_NAMES) if k == 1 else "ptk::knn_reg_kernel / ptk::knn_kernel",
+                        "kernel_ms": round(kernel_ms, 4), "reorder_ms": round(prof["reorder_ms"] / launches, 4),
+                        "other_ms": round(prof["other_ms"] / launches, 4),
+                        "bytes_per_query": round(b_per_q, 1), "queries_per_launch": int(q_per_launch),
+                        "visits_per_query": {kk: round(v, 2) for kk, v in visits.items()}}
 
-        extras = {}
-        if world == 1 and not args.no_extras and k == 1 and not args.n and not args.nq:
-            # (a) the host-pointer entry on pageable arrays: H2D + search + D2H (SURVEY 8d asks for both figures)
-            hsteps = 5
-            warm = [tree.search_knn(q, 1) for _ in range(3)]  # (the wrapper's pool of page-locked blocks fills: two
-            del warm                                           # result arrays are alive at a time in the loop below)
-            t0 = time.perf_counter()
-            for _ in range(hsteps):
-                host_rows = tree.search_knn(q, 1)
-            hdt = (time.perf_counter() - t0) / hsteps
-            extras["host_buffers"] = {"value": round(nq / hdt / 1e6, 3), "unit": "Mqueries/s",
-                                      "ms_per_step": round(hdt * 1e3, 4), "steps": hsteps,
-                                      "what": "rows = tree.search_knn(q, 1) on a pageable numpy query array: 86 MB up, "
-                                              "search, 58 MB down; a new result array every call, as search_knn(pts, k) "
-                                              "of the reference's module returns one (def_kd_tree.cpp:73-82) -- built on "
-                                              "a page-locked block of the wrapper's pool that the device writes directly",
-                                      "rows_equal_device_run": bool(host_rows.tobytes() == res.tobytes())}
-            # the overload that fills the caller's array (search_knn(pts, k, nns), def_kd_tree.cpp): a PAGEABLE numpy
-            # array of the caller's own here: the rows are staged through the handle's pinned ring
-            own_rows = np.empty(nq, dtype=pt.NEIGHBOR)
-            tree.search_knn(q, 1, own_rows)
-            t0 = time.perf_counter()
-            for _ in range(hsteps):
-                tree.search_knn(q, 1, own_rows)
-            hdt2 = (time.perf_counter() - t0) / hsteps
-            extras["host_buffers"]["result_array_handed_in"] = {
-                "value": round(nq / hdt2 / 1e6, 3), "ms_per_step": round(hdt2 * 1e3, 4),
-                "what": "search_knn(q, 1, nns) with nns a pageable numpy array of the caller",
-                "rows_equal_device_run": bool(own_rows.tobytes() == res.tobytes())}
-            del host_rows, own_rows
-            # queries kept in page-locked memory as well (pt.empty_pinned): no staging in either direction
-            q_pin = pt.empty_pinned(q.shape, q.dtype)
-            q_pin[...] = q
-            pin_rows = tree.search_knn(q_pin, 1)
-            t0 = time.perf_counter()
-            for _ in range(hsteps):
-                pin_rows = tree.search_knn(q_pin, 1)
-            hdt3 = (time.perf_counter() - t0) / hsteps
-            extras["host_buffers"]["queries_page_locked_too"] = {
-                "value": round(nq / hdt3 / 1e6, 3), "ms_per_step": round(hdt3 * 1e3, 4),
-                "rows_equal_device_run": bool(pin_rows.tobytes() == res.tobytes())}
-            del pin_rows
-            # ... and the caller's OWN pageable arrays page-locked in place for the duration (ptk_host_register): what an
-            # application with long-lived buffers does instead of allocating from ptk_host_alloc
-            nns_reg = np.empty(nq, dtype=pt.NEIGHBOR)
-            with pt.registered(q), pt.registered(nns_reg):
-                tree.search_knn(q, 1, nns_reg)
+            extras = {}
+            if world == 1 and not args.no_extras and k == 1 and not args.n and not args.nq:
+                # (a) the host-pointer entry on pageable arrays: H2D + search + D2H (SURVEY 8d asks for both figures)
+                hsteps = 5
+                warm = [tree.search_knn(q, 1) for _ in range(3)]  # (the wrapper's pool of page-locked blocks fills: two
+                del warm                                           # result arrays are alive at a time in the loop below)
                 t0 = time.perf_counter()
                 for _ in range(hsteps):
+                    host_rows = tree.search_knn(q, 1)
+                hdt = (time.perf_counter() - t0) / hsteps
+                extras["host_buffers"] = {"value": round(nq / hdt / 1e6, 3), "unit": "Mqueries/s",
+                                          "ms_per_step": round(hdt * 1e3, 4), "steps": hsteps,
+                                          "what": "rows = tree.search_knn(q, 1) on a pageable numpy query array: 86 MB up, "
+                                                  "search, 58 MB down; a new result array every call, as search_knn(pts, k) "
+                                                  "of the reference's module returns one (def_kd_tree.cpp:73-82) -- built on "
+                                                  "a page-locked block of the wrapper's pool that the device writes directly",
+                                          "rows_equal_device_run": bool(host_rows.tobytes() == res.tobytes())}
+                # the overload that fills the caller's array (search_knn(pts, k, nns), def_kd_tree.cpp): a PAGEABLE numpy
+                # array of the caller's own here: the rows are staged through the handle's pinned ring
+                own_rows = np.empty(nq, dtype=pt.NEIGHBOR)
+                tree.search_knn(q, 1, own_rows)
+                t0 = time.perf_counter()
+                for _ in range(hsteps):
+                    tree.search_knn(q, 1, own_rows)
+                hdt2 = (time.perf_counter() - t0) / hsteps
+                extras["host_buffers"]["result_array_handed_in"] = {
+                    "value": round(nq / hdt2 / 1e6, 3), "ms_per_step": round(hdt2 * 1e3, 4),
+                    "what": "search_knn(q, 1, nns) with nns a pageable numpy array of the caller",
+                    "rows_equal_device_run": bool(own_rows.tobytes() == res.tobytes())}
+                del host_rows, own_rows
+                # queries kept in page-locked memory as well (pt.empty_pinned): no staging in either direction
+                q_pin = pt.empty_pinned(q.shape, q.dtype)
+                q_pin[...] = q
+                pin_rows = tree.search_knn(q_pin, 1)
+                t0 = time.perf_counter()
+                for _ in range(hsteps):
+                    pin_rows = tree.search_knn(q_pin, 1)
+                hdt3 = (time.perf_counter() - t0) / hsteps
+                extras["host_buffers"]["queries_page_locked_too"] = {
+                    "value": round(nq / hdt3 / 1e6, 3), "ms_per_step": round(hdt3 * 1e3, 4),
+                    "rows_equal_device_run": bool(pin_rows.tobytes() == res.tobytes())}
+                del pin_rows
+                # ... and the caller's OWN pageable arrays page-locked in place for the duration (ptk_host_register): what an
+                # application with long-lived buffers does instead of allocating from ptk_host_alloc
+                nns_reg = np.empty(nq, dtype=pt.NEIGHBOR)
+                with pt.registered(q), pt.registered(nns_reg):
                     tree.search_knn(q, 1, nns_reg)
-                hdt4 = (time.perf_counter() - t0) / hsteps
-            extras["host_buffers"]["callers_arrays_registered"] = {
-                "value": round(nq / hdt4 / 1e6, 3), "ms_per_step": round(hdt4 * 1e3, 4),
-                "what": "search_knn(q, 1, nns) with the caller's numpy arrays page-locked in place (pt.registered)",
-                "rows_equal_device_run": bool(nns_reg.tobytes() == res.tobytes())}
-            del nns_reg
-            # knn = 16 through the same entry (0.92 GB of rows down)
-            warm = [tree.search_knn(q, 16) for _ in range(2)]
-            del warm
-            t0 = time.perf_counter()
-            for _ in range(3):
-                rows16 = tree.search_knn(q, 16)
-            hdt16 = (time.perf_counter() - t0) / 3
-            extras["host_buffers"]["knn16"] = {"value": round(nq / hdt16 / 1e6, 3), "ms_per_step": round(hdt16 * 1e3, 3),
-                                               "what": "rows = tree.search_knn(q, 16): 86 MB up, 922 MB of rows down"}
-            del rows16, q_pin
-            # (a2) one shard of configs[3] (strong scaling decided on one GPU) and its rows against the full batch
-            sh8 = shard_entry(pt, oracle, pts, q, tree, args.leaf, 8, b_per_q)
-            sh8["rows_equal_full_batch"] = bool(sh8.pop("rows").tobytes() == res[:sh8["queries"]].tobytes())
-            extras["shard_of_8"] = sh8
-            # (a3) what a second creation of the same handle takes (the first pays for loading the code object)
-            t0 = time.perf_counter()
-            tree_b = pt.KdTree(pts, pt.Metric.L2Squared, args.leaf, device=local_rank)
-            create["steady_s"] = round(time.perf_counter() - t0, 3)
-            create["steady_phases"] = {k_: round(v, 3) for k_, v in tree_b.create_phases().items()}
-            create["what"] = ("KdTree(points): build (partitions of the top levels on the device, the subtrees below by the "
-                              "host threads of the library; phase host_build_s), re-encoding for the device, upload + "
-                              "point gather; first = first handle of the process (the code object loads from "
-                              "pt.warmup(device) on, beside the generation of the clouds)")
-            del tree_b
-            extras["create"] = create
-            # (b) config 3 on the same clouds
-            if args.cloud == "L" and args.order == "generated":
-                extras["config3"] = config3_entries(pt, oracle, pts, q, tree, dq, args.leaf, 100_000)
-            if k == 1:
-                extras["approximate"] = approximate_entry(pt, oracle, pts, q, tree, dq, args.leaf, 1.05, 10, 20_000)
-            if args.cloud == "L" and args.order == "generated":  # (the other metrics and float64 on the headline clouds)
-                try:
-                    extras.update(metrics_and_f64_entries(pt, oracle, pts, q, args.leaf, local_rank, 5, 20_000))
-                except Exception as exc:  # noqa: BLE001 -- a leg that fails says so instead of taking the line with it
-                    extras["metrics"] = {"error": repr(exc)}
-            # (c) the headline search on the other query order and on the other cloud
-            also = []
-            other_order = "morton" if args.order == "generated" else "generated"
-            also.append(also_entry(pt, ds, oracle, args.cloud, other_order, pts, q, tree, args.leaf, 10, 100_000))
-            oc = "U" if args.cloud == "L" else "L"
-            del dq
-            pts2, q2 = ds.config2_clouds(oc, n, nq)
-            tree2 = pt.KdTree(pts2, pt.Metric.L2Squared, args.leaf, device=local_rank)
-            for order in ("generated", "morton"):
-                also.append(also_entry(pt, ds, oracle, oc, order, pts2, q2, tree2, args.leaf, 10, 100_000))
-            del tree2, pts2, q2
-            if args.cloud == "L":  # tie-prone data: every coordinate a multiple of 0.1
-                also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 0.1, local_rank, 10, 100_000))
-                # ... and of 1.0: piles of up to 600 coincident points (the k = 1 view without them, ptk_piles.hpp)
-                also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 1.0, local_rank, 10, 100_000))
-                also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 1.0, local_rank, 10, 100_000, shift=0.3))
-            extras["also"] = also
-            # (d) BASELINE configs[4]
-            extras["config5"] = config5_entry(pt, ds, local_rank)
+                    t0 = time.perf_counter()
+                    for _ in range(hsteps):
+                        tree.search_knn(q, 1, nns_reg)
+                    hdt4 = (time.perf_counter() - t0) / hsteps
+                extras["host_buffers"]["callers_arrays_registered"] = {
+                    "value": round(nq / hdt4 / 1e6, 3), "ms_per_step": round(hdt4 * 1e3, 4),
+                    "what": "search_knn(q, 1, nns) with the caller's numpy arrays page-locked in place (pt.registered)",
+                    "rows_equal_device_run": bool(nns_reg.tobytes() == res.tobytes())}
+                del nns_reg
+                # knn = 16 through the same entry (0.92 GB of rows down)
+                warm = [tree.search_knn(q, 16) for _ in range(2)]
+                del warm
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    rows16 = tree.search_knn(q, 16)
+                hdt16 = (time.perf_counter() - t0) / 3
+                extras["host_buffers"]["knn16"] = {"value": round(nq / hdt16 / 1e6, 3), "ms_per_step": round(hdt16 * 1e3, 3),
+                                                   "what": "rows = tree.search_knn(q, 16): 86 MB up, 922 MB of rows down"}
+                del rows16, q_pin
+                # (a2) one shard of configs[3] (strong scaling decided on one GPU) and its rows against the full batch
+                sh8 = shard_entry(pt, oracle, pts, q, tree, args.leaf, 8, b_per_q)
+                sh8["rows_equal_full_batch"] = bool(sh8.pop("rows").tobytes() == res[:sh8["queries"]].tobytes())
+                extras["shard_of_8"] = sh8
+                # (a3) what a second creation of the same handle takes (the first pays for loading the code object)
+                t0 = time.perf_counter()
+                tree_b = pt.KdTree(pts, pt.Metric.L2Squared, args.leaf, device=local_rank)
+                create["steady_s"] = round(time.perf_counter() - t0, 3)
+                create["steady_phases"] = {k_: round(v, 3) for k_, v in tree_b.create_phases().items()}
+                create["what"] = ("KdTree(points): build (partitions of the top levels on the device, the subtrees below by the "
+                                  "host threads of the library; phase host_build_s), re-encoding for the device, upload + "
+                                  "point gather; first = first handle of the process (the code object loads from "
+                                  "pt.warmup(device) on, beside the generation of the clouds)")
+                del tree_b
+                extras["create"] = create
+                # (b) config 3 on the same clouds
+                if args.cloud == "L" and args.order == "generated":
+                    extras["config3"] = config3_entries(pt, oracle, pts, q, tree, dq, args.leaf, 100_000)
+                if k == 1:
+                    extras["approximate"] = approximate_entry(pt, oracle, pts, q, tree, dq, args.leaf, 1.05, 10, 20_000)
+                if args.cloud == "L" and args.order == "generated":  # (the other metrics and float64 on the headline clouds)
+                    try:
+                        extras.update(metrics_and_f64_entries(pt, oracle, pts, q, args.leaf, local_rank, 5, 20_000))
+                    except Exception as exc:  # noqa: BLE001 -- a leg that fails says so instead of taking the line with it
+                        extras["metrics"] = {"error": repr(exc)}
+                # (c) the headline search on the other query order and on the other cloud
+                also = []
+                other_order = "morton" if args.order == "generated" else "generated"
+                also.append(also_entry(pt, ds, oracle, args.cloud, other_order, pts, q, tree, args.leaf, 10, 100_000))
+                oc = "U" if args.cloud == "L" else "L"
+                del dq
+                pts2, q2 = ds.config2_clouds(oc, n, nq)
+                tree2 = pt.KdTree(pts2, pt.Metric.L2Squared, args.leaf, device=local_rank)
+                for order in ("generated", "morton"):
+                    also.append(also_entry(pt, ds, oracle, oc, order, pts2, q2, tree2, args.leaf, 10, 100_000))
+                del tree2, pts2, q2
+                if args.cloud == "L":  # tie-prone data: every coordinate a multiple of 0.1
+                    also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 0.1, local_rank, 10, 100_000))
+                    # ... and of 1.0: piles of up to 600 coincident points (the k = 1 view without them, ptk_piles.hpp)
+                    also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 1.0, local_rank, 10, 100_000))
+                    also.append(quantised_entry(pt, ds, oracle, pts, q, args.leaf, 1.0, local_rank, 10, 100_000, shift=0.3))
+                extras["also"] = also
+                # (d) BASELINE configs[4]
+                extras["config5"] = config5_entry(pt, ds, local_rank)
 
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            cpu = cpu_baseline_subprocess(args)
+            if not args.no_cpu_baseline and world == 1:
+                cpu = cpu_baseline_subprocess(args)
 
         def parallelism(w):
             return ((f"{world} x {nq} queries (one full batch per GPU), tree replicated" if w
@@ -1177,14 +1216,17 @@ def main():
             result["weak" if other["weak"] else "strong"] = {
                 "value": round(other["value"], 3), "unit": "Mqueries/s", "ms_per_step": round(other["ms_per_step"], 4),
                 "queries_per_step": int(other["total"]), "parallelism": parallelism(other["weak"])}
-        if world > 1 and pt.device_count() >= world and not args.no_extras:
+        if args.full and world > 1 and pt.device_count() >= world and not args.no_extras:
             # (the other ranks wait for the key below on the host, their devices idle: a collective barrier would
             # keep a polling kernel on every one of them while the child measures)
             result["single_process"] = run_single_process_form(args, world)
+        if not args.full:  # the headline alone: nothing here was measured or checked
+            for key in ("parity_sample_ok", "roofline", "pipelined", "cpu_baseline"):
+                del result[key]
         result.update(extras)
         print(json.dumps(result), flush=True)
     if world > 1:
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             try:
                 from datetime import timedelta
 
@@ -1197,7 +1239,7 @@ def main():
                 pass
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and result is not None and not result["parity_sample_ok"]:
+    if rank == 0 and args.full and result is not None and not result["parity_sample_ok"]:
         raise SystemExit("parity check failed")
 
 

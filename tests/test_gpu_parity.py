@@ -1229,7 +1229,7 @@ def test_all_devices_of_the_node(gpu, monkeypatch):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_dev}",
            "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(root, "bench.py"), "--gpus", str(n_dev),
-           "--steps", "3", "--warmup", "1", "--n", "400000", "--nq", "200003", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--n", "400000", "--nq", "200003", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     import json
