@@ -206,6 +206,9 @@ struct ptk_api<float> {
   static int knn(tree const* t, float const* q, std::uint64_t nq, std::uint32_t k, float e, neighbor* out) {
     return ptk_search_knn(t, q, nq, k, e, out);
   }
+  static int knn_within(tree const* t, float const* q, std::uint64_t nq, std::uint32_t k, float r, neighbor* out) {
+    return ptk_search_knn_within(t, q, nq, k, r, out);
+  }
   static int radius(tree const* t, float const* q, std::uint64_t nq, float r, float e, int sort,
                     std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius(t, q, nq, r, e, sort, offsets, out);
@@ -223,6 +226,9 @@ struct ptk_api<double> {
   static int set_metric(tree* t, int m) { return ptk_tree64_set_metric(t, m); }
   static int knn(tree const* t, double const* q, std::uint64_t nq, std::uint32_t k, double e, neighbor* out) {
     return ptk_search64_knn(t, q, nq, k, e, out);
+  }
+  static int knn_within(tree const* t, double const* q, std::uint64_t nq, std::uint32_t k, double r, neighbor* out) {
+    return ptk_search64_knn_within(t, q, nq, k, r, out);
   }
   static int radius(tree const* t, double const* q, std::uint64_t nq, double r, double e, int sort,
                     std::uint64_t* offsets, neighbor** out) {

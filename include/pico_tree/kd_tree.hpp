@@ -19,6 +19,7 @@
 //! visitors, other metrics, double) run on the host, as in the reference.
 
 #include <algorithm>
+#include <cmath>
 #include <fstream>
 #include <iostream>
 #include <iterator>
@@ -164,6 +165,33 @@ class kd_tree {
     search_knn(x, knn.begin(), knn.end());
   }
 
+  //! The k nearest points closer than \p radius (metric units: squared for the
+  //! default metric): the search_knn row of min(k, number of points) entries
+  //! cut at the first distance >= radius; \p knn is resized to the hits.  The
+  //! k-list starts at radius * (1 + 2^-10) instead of the largest scalar, so the
+  //! search prunes with min(k-th, that bound); metric_lpinf /
+  //! metric_lninf and the topological metrics, whose box distance is no lower
+  //! bound of the point distances, search unseeded.
+  template <typename P_>
+  inline void search_knn_within(
+      P_ const& x,
+      size_type const k,
+      scalar_type const radius,
+      std::vector<neighbor_type>& knn) const {
+    knn.resize(std::min(k, view().size()));
+    if (knn.empty()) return;
+    internal::knn_visitor<typename std::vector<neighbor_type>::iterator> v(knn.begin(), knn.end());
+    constexpr bool seeded = std::is_same_v<Metric_, metric_l2_squared> || std::is_same_v<Metric_, metric_l1>;
+    scalar_type const seed = radius * (scalar_type(1) + scalar_type(1) / scalar_type(1024));
+    if (seeded && (radius == scalar_type(0) || std::isnormal(radius)) && std::isfinite(seed)) {
+      std::fill(knn.begin(), knn.end(), neighbor_type(index_type(-1), seed));
+    }
+    search_nearest(x, v);
+    size_type n = 0;
+    while (n < knn.size() && knn[n].index != index_type(-1) && knn[n].distance < radius) ++n;
+    knn.resize(n);
+  }
+
   template <typename P_, typename RandomAccessIterator_>
   inline void search_knn(
       P_ const& x,
@@ -263,6 +291,17 @@ class kd_tree {
       scalar_type const e,
       neighbor_type* out) const {
     batched_knn(queries, k, e, out);
+  }
+
+  //! out[i * k + j]: row i of search_knn_within -- the k nearest points closer
+  //! than \p radius -- padded to k entries with {-1, radius}.  Any k >= 1.
+  template <typename QuerySpace_>
+  inline void search_knn_within(
+      QuerySpace_ const& queries,
+      size_type const k,
+      scalar_type const radius,
+      neighbor_type* out) const {
+    batched_knn_within(queries, k, radius, out);
   }
 
   //! out[i] = all neighbours of query i within \p radius.
@@ -461,6 +500,33 @@ class kd_tree {
         } else {
           search_knn(x, e, out + i * k, out + (i + 1) * k);
         }
+      });
+    }
+  }
+
+  template <typename QuerySpace_>
+  void batched_knn_within(
+      QuerySpace_ const& queries, size_type k, scalar_type radius, neighbor_type* out) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    try {
+      internal::ptk_check(
+          api::knn_within(
+              device(), q.data(), q.rows(), static_cast<std::uint32_t>(k), radius,
+              reinterpret_cast<typename api::neighbor*>(out)),
+          "ptk_search_knn_within");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(q.rows(), [&](size_type i) {
+        row_point x = make_row(q.data() + i * q.cols(), q.cols());
+        std::vector<neighbor_type> row;
+        search_knn_within(x, k, radius, row);
+        std::copy(row.begin(), row.end(), out + i * k);
+        std::fill(out + i * k + row.size(), out + (i + 1) * k, neighbor_type(index_type(-1), radius));
       });
     }
   }

@@ -220,6 +220,23 @@ int ptk_search_knn_device(const ptk_tree* tree, const float* d_queries,
                           uint64_t nq, uint32_t k, float e,
                           ptk_neighbor* d_out, void* stream);
 
+/* ---- the k nearest within a radius --------------------------------------- */
+
+/* Results contract: row i is the reference's search_knn(q_i, min(k, n_points)) row,
+ * keeping only the entries with distance < radius (strict, as the radius search:
+ * search_visitor.hpp:141), in the same order, padded to k entries with {index = -1,
+ * distance = radius}.  radius is in metric units (squared for L2^2).  Every k >= 1 is valid,
+ * k > n_points included; k == 0 and a radius that is NaN or negative are PTK_ERR_INVALID.  The
+ * search is exact (no e).  The k-list starts at the radius, so no query's search reaches
+ * (much) past it.  Topological metrics: PTK_ERR_UNSUPPORTED (ptk_host_search_knn_within serves
+ * them).  The host form moves the batch through the handle's device buffers; the device form
+ * only enqueues on `stream`, as ptk_search_knn_device. */
+int ptk_search_knn_within(const ptk_tree* tree, const float* queries, uint64_t nq,
+                          uint32_t k, float radius, ptk_neighbor* out);
+int ptk_search_knn_within_device(const ptk_tree* tree, const float* d_queries,
+                                 uint64_t nq, uint32_t k, float radius,
+                                 ptk_neighbor* d_out, void* stream);
+
 /* ---- radius search (ragged output) ------------------------------------ */
 
 /* Pass 1: counts[i] = number of points with distance < radius (strict,
@@ -285,6 +302,8 @@ void ptk_free(void* p);
  * batched members loop their own per-query members).  float32 handles. */
 int ptk_host_search_knn(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, uint32_t k,
                         float e, ptk_neighbor* out);
+int ptk_host_search_knn_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
+                               uint32_t k, float radius, ptk_neighbor* out);
 int ptk_host_search_radius(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
                            float e, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
@@ -358,6 +377,12 @@ int ptk_search64_knn(const ptk_tree64* tree, const double* queries, uint64_t nq,
 int ptk_search64_knn_device(const ptk_tree64* tree, const double* d_queries,
                             uint64_t nq, uint32_t k, double e,
                             ptk_neighbor64* d_out, void* stream);
+/* As ptk_search_knn_within / ptk_search_knn_within_device (the pad: {-1, radius} in double). */
+int ptk_search64_knn_within(const ptk_tree64* tree, const double* queries, uint64_t nq,
+                            uint32_t k, double radius, ptk_neighbor64* out);
+int ptk_search64_knn_within_device(const ptk_tree64* tree, const double* d_queries,
+                                   uint64_t nq, uint32_t k, double radius,
+                                   ptk_neighbor64* d_out, void* stream);
 /* As ptk_search_radius: *out is malloc'ed by the library (ptk_free).  With
  * sort != 0 rows ascend by distance, equal distances by index. */
 int ptk_search64_radius(const ptk_tree64* tree, const double* queries,

@@ -96,6 +96,8 @@ _SIGNATURES = {
     "ptk_search_knn": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_search_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p,
                                       c_void_p]),
+    "ptk_search_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
+    "ptk_search_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p]),
     "ptk_search_radius_count": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p]),
     "ptk_search_radius_fill": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p,
                                        c_void_p, c_int]),
@@ -111,6 +113,7 @@ _SIGNATURES = {
     "ptk_search_box_fill_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
     "ptk_free": (None, [c_void_p]),
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
+    "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_radius": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_float, c_int,
                                        c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -130,6 +133,8 @@ _SIGNATURES = {
                                                           POINTER(c_void_p)]),
     "ptk_search64_knn": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
     "ptk_search64_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
+    "ptk_search64_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
+    "ptk_search64_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_radius": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_double, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "ptk_search64_box": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -804,6 +809,56 @@ class KdTree:
         self._served(search(self._h, q.ctypes.data, nq, k, self._real(e), nns.ctypes.data),
                      lambda lib: lib.ptk_host_search_knn(self._h, self._pts.ctypes.data, q.ctypes.data, nq, k,
                                                          np.float32(e), nns.ctypes.data))
+        return nns
+
+    def search_knn_within(self, pts, k: int, radius: float, nns=None):
+        """``search_knn_within(pts, k, radius[, nns])`` -- the k nearest points closer than ``radius``.
+
+        Row i is :meth:`search_knn`'s row of ``min(k, npts)`` entries, keeping only the entries with
+        distance ``< radius`` (metric units: squared for L2 squared), padded to k entries with
+        ``(index -1, distance radius)`` (``ptk_search_knn_within`` / ``ptk_search64_knn_within``).  Exact;
+        float32 and float64 trees.  Layouts as :meth:`search_knn`: host arrays give numpy rows (``(k, nq)`` for
+        column-major queries), a torch CUDA tensor gives a :class:`DeviceNeighbors`.
+        """
+        k = int(k)
+        r = self._real(radius)
+        NB = self._neighbor
+        if _is_torch(pts):
+            import torch
+            tq, traw = (torch.float64, torch.int64) if self._f64 else (torch.float32, torch.int32)
+            if pts.dtype != tq or pts.dim() != 2 or pts.shape[1] != self._sdim:
+                raise ValueError(f"queries must be a {self._dtype.name} (nq, sdim) tensor")
+            if not pts.is_cuda or not pts.is_contiguous():
+                raise ValueError("queries must be a contiguous CUDA tensor")
+            nq = pts.shape[0]
+            out = nns.raw if isinstance(nns, DeviceNeighbors) else nns
+            if out is None:
+                # (float64: the records carry 4 bytes of padding, zeroed so that index reads as an int64)
+                out = (torch.zeros if self._f64 else torch.empty)((nq, k, 2), dtype=traw, device=pts.device)
+            if out.dtype != traw or tuple(out.shape) != (nq, k, 2) or not out.is_contiguous():
+                raise ValueError(f"nns must be a contiguous {traw} (nq, k, 2) tensor")
+            stream = torch.cuda.current_stream(pts.device).cuda_stream
+            _check(self._fn("ptk_search_knn_within_device")(self._h, pts.data_ptr(), nq, k, r, out.data_ptr(), stream))
+            return DeviceNeighbors(out)
+        q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
+        nq = q.shape[0]
+        shape = (nq,) if k == 1 else ((nq, k) if pts.flags.c_contiguous else (k, nq))
+        if nns is None:
+            nns = np.zeros(shape, dtype=NB) if self._f64 else np.empty(shape, dtype=NB)
+        elif not isinstance(nns, np.ndarray) or nns.dtype != NB:
+            raise ValueError("unexpected dtype_neighbor for data")
+        elif nns.size != nq * k or not nns.flags.c_contiguous:
+            try:
+                nns.resize(shape, refcheck=False)
+            except ValueError:
+                nns = np.zeros(shape, dtype=NB)
+        # (column-major callers: row i of the search is column i of the output, as search_knn)
+        rows = nns if k == 1 or pts.flags.c_contiguous else np.zeros((nq, k), dtype=NB)
+        self._served(self._fn("ptk_search_knn_within")(self._h, q.ctypes.data, nq, k, r, rows.ctypes.data),
+                     lambda lib: lib.ptk_host_search_knn_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq, k,
+                                                                np.float32(radius), rows.ctypes.data))
+        if rows is not nns:
+            nns.reshape(-1)[:] = rows.reshape(-1)
         return nns
 
     def _served(self, status: int, host_loop) -> None:

@@ -1745,6 +1745,113 @@ static int search_knn_host(const ptk_tree* t, const float* q, uint64_t nq, uint3
   return PTK_OK;
 }
 
+// ---- the k nearest within a radius -------------------------------------------
+
+// The pruning bound the bounded k-list starts at: radius * (1 + 2^-10), the margin knn1_coop_kernel derives for the
+// ulps the incremental box distance may drift by (ptk_kernels_coopk.hpp).  FLT_MAX -- the plain search, masked when
+// the rows are stored -- where that argument does not hold: metrics whose box distance is no lower bound of the point
+// distances (metric_lpinf / metric_lninf), a radius that is subnormal or whose margin overflows.
+static float within_seed(const ptk_tree* t, float radius) {
+  const int m = t->metric.load();
+  if (m == PTK_METRIC_LPINF || m == PTK_METRIC_LNINF) return 3.402823466e+38f;
+  if (radius != 0.0f && !std::isnormal(radius)) return 3.402823466e+38f;
+  const float seed = radius * (1.0f + 0x1p-10f);
+  return std::isfinite(seed) ? seed : 3.402823466e+38f;
+}
+
+int ptk_search_knn_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float radius,
+                                 ptk_neighbor* d_out, void* stream) {
+  int rc = check_search(t, d_q, nq);
+  if (rc != PTK_OK) return rc;
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // (pieces of at most PTK_MAX_BATCH queries, as ptk_search_knn_device)
+  const uint64_t piece = (uint64_t)std::max(1, env_int("PTK_MAX_BATCH", 1 << 25));
+  if (nq > piece) {
+    for (uint64_t done = 0; done < nq; done += piece) {
+      const uint64_t n = std::min(piece, nq - done);
+      rc = ptk_search_knn_within_device(t, d_q + done * t->dim, n, k, radius, d_out + done * k, stream);
+      if (rc != PTK_OK) return rc;
+    }
+    return PTK_OK;
+  }
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
+  if (deep_tree(t)) {  // the deep stack class: the margin assumes shallower trees -- unseeded, masked at store
+    const DeepPlan plan = deep_plan(t, nq);
+    Scratch scratch(t, s, /*per_stream=*/true);
+    rc = scratch.reserve(plan.bytes());
+    if (rc != PTK_OK) return rc;
+    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
+    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
+    Timer timer(t, s);
+    for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
+      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
+      if (t->dim > 3) {
+        ptk::DevTreeND dev = t->dev_nd;
+        dev.deep_spill = spill;
+        dev.deep_cap = plan.cap;
+        rc = ptkf::knn_nd_within_deep(t, dev, d_q + lo * t->dim, n, k, radius, o + lo * k, s);
+      } else {
+        ptk::DevTree dev = t->dev;
+        dev.deep_spill = spill;
+        dev.deep_cap = plan.cap;
+        rc = ptkf::knn_within_deep(t, dev, d_q + lo * t->dim, n, k, radius, o + lo * k, s);
+      }
+      if (rc != PTK_OK) return rc;
+    }
+    timer.stop(0, nq);
+    return PTK_OK;
+  }
+  const float seed = within_seed(t, radius);
+  const bool reorder = want_reorder(t, nq);
+  Scratch scratch(t, s, /*per_stream=*/true);
+  rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+  if (rc != PTK_OK) return rc;
+  uint32_t* perm = nullptr;
+  if (reorder) {  // (as the general k-NN kernels: the expensive queries to the front of the launch)
+    rc = make_permutation(t, d_q, nq, s, scratch, &perm, t->dim <= 3 ? ptk::kCellsEmptyFirst : 0u);
+    if (rc != PTK_OK) return rc;
+  }
+  if (t->dim > 3) return ptkf::knn_nd_within(t, d_q, perm, nq, k, seed, radius, o, s);
+  return ptkf::knn_within(t, d_q, perm, nq, k, seed, radius, o, s);
+}
+
+// Host buffers: the batch goes up, is searched on one stream of the handle and comes down, under the handle's I/O lock.
+int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32_t k, float radius, ptk_neighbor* out) {
+  int rc = check_search(t, q, nq);
+  if (rc != PTK_OK) return rc;
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t row_in = (size_t)t->dim * sizeof(float), row_out = (size_t)k * sizeof(ptk_neighbor);
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  rc = grow_device_block(&io.d_in, &io.in_capacity, (size_t)nq * row_in);
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, (size_t)nq * row_out);
+  if (rc != PTK_OK) return rc;
+  PTK_HIP(hipMemcpyAsync(io.d_in, q, (size_t)nq * row_in, hipMemcpyHostToDevice, io.search[0]));
+  rc = ptk_search_knn_within_device(t, reinterpret_cast<const float*>(io.d_in), nq, k, radius,
+                                    reinterpret_cast<ptk_neighbor*>(io.d_out), io.search[0]);
+  if (rc != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return rc;
+  }
+  PTK_HIP(hipMemcpyAsync(out, io.d_out, (size_t)nq * row_out, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  return PTK_OK;
+}
+
 // ---- radius -------------------------------------------------------------------------------
 
 static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, float e, bool fill,

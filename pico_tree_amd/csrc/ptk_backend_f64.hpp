@@ -363,6 +363,49 @@ int launch_knn64(const ptk_tree64* t, const double* d_q, const uint32_t* perm, u
   return PTK_OK;
 }
 
+// search_knn_within: launch_knn64's kernels in their bounded form; never capped.
+template <class M>
+int launch_knn64_within(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq, uint32_t k,
+                        double seed, double radius, ptk::Neighbor64* d_out, hipStream_t s, Stack64Lease& lease) {
+  if constexpr (M::kTopo) {
+    return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  } else {
+  const bool d3 = t->dim <= 3;
+  const size_t smem = ptk::lds64_bytes(d3 ? 0 : 2, t->dim);
+  if (smem > 160 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dim %u needs %zu bytes of LDS per wavefront (> 160 KiB)", t->dim, smem);
+  int rc = PTK_OK;
+  // (register list for k <= 64 with dim <= 3, k <= 32 otherwise -- the VGPR budget of launch_knn64)
+  const int reg = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 && d3 ? 64 : 0))));
+#define PTK_LAUNCH64_WITHIN(KERNEL)                                                                                   \
+  do {                                                                                                                \
+    rc = allow_lds(KERNEL, smem);                                                                                     \
+    if (rc != PTK_OK) return rc;                                                                                      \
+    for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {                                                               \
+      const uint64_t n = std::min(lease.piece, nq - q0);                                                              \
+      hipLaunchKernelGGL(KERNEL, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k,   \
+                         d_out, lease.stack, t->slots, seed, radius);                                                \
+    }                                                                                                                 \
+  } while (0)
+  if (d3) {
+    if (reg == 4) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 4, true>));
+    else if (reg == 8) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 8, true>));
+    else if (reg == 16) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 16, true>));
+    else if (reg == 32) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 32, true>));
+    else if (reg == 64) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 64, true>));
+    else PTK_LAUNCH64_WITHIN((ptk::knn64_within_kernel<M, true>));
+  } else {
+    if (reg == 4) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 4, false>));
+    else if (reg == 8) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 8, false>));
+    else if (reg == 16) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 16, false>));
+    else if (reg == 32) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 32, false>));
+    else PTK_LAUNCH64_WITHIN((ptk::knn64_within_kernel<M, false>));
+  }
+#undef PTK_LAUNCH64_WITHIN
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+  }
+}
+
 // ---- the capped k-NN launch + the cooperative search of what it hands over (ptk_kernels_coop64.hpp) ----
 // Far children a query may enter before a wavefront takes it over; 0 = every query runs to its end in its lane.  Exact
 // searches, dim <= 3, metric_l2_squared / metric_l1 (box distances that are lower bounds: knn_coop_kernel), k <= 32 (the
@@ -880,6 +923,66 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
   }
   PTK_WITH_METRIC64(rc = launch_knn64<M>(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
                                          short_tree));
+  return rc;
+}
+
+// search_knn_within (ptk.h).  The list starts at radius * (1 + 2^-10) (as the float32 search); DBL_MAX
+// -- the plain search, masked at store -- for metric_lpinf / metric_lninf, trees deeper than the margin covers
+// (~2 000 levels), a radius that is subnormal or whose margin overflows.
+int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint64_t nq, uint32_t k, double radius,
+                                   ptk_neighbor64* d_out, void* stream) {
+  int rc = check_search64(t, d_q, nq);
+  if (rc != PTK_OK) return rc;
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  const int m = t->metric.load();
+  if (m == PTK_METRIC_SO2 || m == PTK_METRIC_SE2_SQUARED)
+    return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  double seed = radius * (1.0 + 0x1p-10);
+  if (m == PTK_METRIC_LPINF || m == PTK_METRIC_LNINF || t->max_depth > 1024u || (radius != 0.0 && !std::isnormal(radius)) ||
+      !std::isfinite(seed))
+    seed = 1.7976931348623157e+308;
+  Stack64Lease lease(t, s);
+  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
+  rc = lease.acquire(nq, perm_bytes);
+  if (rc != PTK_OK) return rc;
+  const uint32_t* perm = nullptr;
+  rc = make_permutation64(t, d_q, nq, s, lease, &perm, /*long_first=*/true);
+  if (rc != PTK_OK) return rc;
+  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, seed, radius, reinterpret_cast<ptk::Neighbor64*>(d_out),
+                                                s, lease));
+  return rc;
+}
+
+int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, double radius,
+                            ptk_neighbor64* out) {
+  int rc = check_search64(t, q, nq);
+  if (rc != PTK_OK) return rc;
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bq, bo;
+  const size_t qbytes = (size_t)nq * t->dim * sizeof(double), obytes = (size_t)nq * k * sizeof(ptk_neighbor64);
+  hipError_t he = bq.get(t, 0, qbytes);
+  if (he == hipSuccess) he = bo.get(t, 1, obytes);
+  double* d_q = reinterpret_cast<double*>(bq.p);
+  ptk_neighbor64* d_out = reinterpret_cast<ptk_neighbor64*>(bo.p);
+  if (he == hipSuccess) he = hipMemset(d_out, 0, obytes ? obytes : 16);  // padding bytes of the records
+  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    rc = ptk_search64_knn_within_device(t, d_q, nq, k, radius, d_out, nullptr);
+    if (rc == PTK_OK) he = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return rc;
 }
 

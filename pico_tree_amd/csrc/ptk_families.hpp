@@ -19,6 +19,12 @@ int knn_rows(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t
              ptk::Neighbor* d_out, hipStream_t s);
 int knn_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float e,
              ptk::Neighbor* d_out, hipStream_t s);
+// search_knn_within: `seed` is the pruning bound the list starts at (FLT_MAX: unseeded), `radius` the
+// bound of the stored entries; the deep forms run unseeded
+int knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed, float radius,
+               ptk::Neighbor* d_out, hipStream_t s);
+int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
+                    ptk::Neighbor* d_out, hipStream_t s);
 void warm_knn();
 // ptk_family_radius.hip: 3-D float32 trees
 int radius_traverse(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e, bool fill,
@@ -51,6 +57,10 @@ int radius_nd_capture(const ptk_tree* t, const float* d_q, const uint32_t* perm,
                       uint64_t* d_counts, const ptk::RadiusCapture& cap, hipStream_t s);
 int radius_nd_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, float radius, float e,
                    bool fill, uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s);
+int knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
+                  float radius, ptk::Neighbor* d_out, hipStream_t s);
+int knn_nd_within_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
+                       ptk::Neighbor* d_out, hipStream_t s);
 void warm_nd();
 // ptk_family_topo.hip: metric_so2 / metric_se2_squared
 int knn_topo(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float e,

@@ -150,6 +150,44 @@ int launch_knn_reg(const ptk_tree* t, const float* d_q, const uint32_t* perm, ui
   return PTK_OK;
 }
 
+// search_knn_within: the register list for k <= 64 -- whatever k is against n_points: an unfilled slot
+// is the pad --, the list in LDS or in the row beyond; never capped (the radius bounds every query's search).
+template <int OVF, class M>
+int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
+                      float radius, ptk::Neighbor* d_out, hipStream_t s) {
+  constexpr int BLOCK = 64;
+  const uint32_t blocks = (uint32_t)((nq + BLOCK - 1) / BLOCK);
+  Timer timer(t, s);
+  if (k <= 64) {
+    constexpr int S = kGenRing;
+    const size_t smem = (size_t)S * BLOCK * 8;
+#define PTK_LAUNCH_REG_WITHIN(KK)                                                                                     \
+  hipLaunchKernelGGL((ptk::knn_reg_within_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, s, \
+                     t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius)
+    if (k <= 4) PTK_LAUNCH_REG_WITHIN(4);
+    else if (k <= 8) PTK_LAUNCH_REG_WITHIN(8);
+    else if (k <= 16) PTK_LAUNCH_REG_WITHIN(16);
+    else if (k <= 32) PTK_LAUNCH_REG_WITHIN(32);
+    else PTK_LAUNCH_REG_WITHIN(64);
+#undef PTK_LAUNCH_REG_WITHIN
+  } else {  // (the LDS budget of launch_knn)
+    constexpr int S = 16;
+    const size_t stack_bytes = (size_t)S * BLOCK * 8, list_bytes = (size_t)k * BLOCK * 8;
+    if (stack_bytes + list_bytes <= (size_t)48 * 1024) {
+      const int lds_rc = allow_lds(ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>, stack_bytes + list_bytes);
+      if (lds_rc != PTK_OK) return lds_rc;
+      hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>), dim3(blocks), dim3(BLOCK),
+                         stack_bytes + list_bytes, s, t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius);
+    } else {
+      hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, false, M>), dim3(blocks), dim3(BLOCK), stack_bytes, s,
+                         t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius);
+    }
+  }
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, nq);
+  return PTK_OK;
+}
+
 
 static __global__ void warm_knn_kernel() {}
 
@@ -178,6 +216,30 @@ int knn_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint6
   PTK_WITH_METRIC({
     hipLaunchKernelGGL((ptk::knn_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s, dev,
                        d_q, t->dim, nullptr, n, k, inv_ratio(e), d_out);
+  });
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+int knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed, float radius,
+               ptk::Neighbor* d_out, hipStream_t s) {
+  int rc = PTK_OK;
+  // (the stack class of the ring each form is launched with: kGenRing for the register list, 16 for the list kernel)
+  if (k <= 64) {
+    PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
+  } else {
+    PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
+  }
+  return rc;
+}
+
+// knn_deep for search_knn_within: unseeded, masked at `radius` when the row is stored.
+int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
+                    ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  PTK_WITH_METRIC({
+    hipLaunchKernelGGL((ptk::knn_within_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s,
+                       dev, d_q, t->dim, nullptr, n, k, d_out, 3.402823466e+38f, radius);
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;

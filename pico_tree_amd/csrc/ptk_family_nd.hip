@@ -54,6 +54,53 @@ int launch_knn_nd(const ptk_tree* t, const float* d_q, const uint32_t* perm, uin
   return PTK_OK;
 }
 
+// search_knn_within: launch_knn_nd's kernels in their bounded form.
+template <int OVF, class M>
+int launch_knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
+                         float radius, ptk::Neighbor* d_out, hipStream_t s) {
+  constexpr int S = 16;
+  const uint32_t blocks = (uint32_t)((nq + 63) / 64);
+  const size_t base = (size_t)S * 64 * 8 + (size_t)t->dim * 64 * 8;
+  if (base > t->lds_per_block)
+    return fail(PTK_ERR_UNSUPPORTED, "dimension %u does not fit the LDS staging of the device search", t->dim);
+  Timer timer(t, s);
+  int rc = PTK_OK;
+  if (k <= 64) {
+#define PTK_LAUNCH_ND_REG_WITHIN(KK)                                                                                   \
+  do {                                                                                                               \
+    rc = allow_lds(ptk::knn_nd_reg_within_kernel<KK, S, OVF, M>, base);                                              \
+    if (rc == PTK_OK)                                                                                                \
+      hipLaunchKernelGGL((ptk::knn_nd_reg_within_kernel<KK, S, OVF, M>), dim3(blocks), dim3(64), base, s, t->dev_nd,  \
+                         d_q, perm, nq, k, d_out, seed, radius);                                                     \
+  } while (0)
+    if (k <= 4) PTK_LAUNCH_ND_REG_WITHIN(4);
+    else if (k <= 8) PTK_LAUNCH_ND_REG_WITHIN(8);
+    else if (k <= 16) PTK_LAUNCH_ND_REG_WITHIN(16);
+    else if (k <= 32) PTK_LAUNCH_ND_REG_WITHIN(32);
+    else PTK_LAUNCH_ND_REG_WITHIN(64);
+#undef PTK_LAUNCH_ND_REG_WITHIN
+  } else {
+    const size_t list_bytes = (size_t)k * 64 * 8;
+    const bool list_lds = base + list_bytes <= 64 * 1024;
+    const size_t smem = base + (list_lds ? list_bytes : 0);
+    if (list_lds) {
+      rc = allow_lds(ptk::knn_nd_within_kernel<S, OVF, true, M>, smem);
+      if (rc == PTK_OK)
+        hipLaunchKernelGGL((ptk::knn_nd_within_kernel<S, OVF, true, M>), dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q,
+                           perm, nq, k, d_out, seed, radius);
+    } else {
+      rc = allow_lds(ptk::knn_nd_within_kernel<S, OVF, false, M>, smem);
+      if (rc == PTK_OK)
+        hipLaunchKernelGGL((ptk::knn_nd_within_kernel<S, OVF, false, M>), dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q,
+                           perm, nq, k, d_out, seed, radius);
+    }
+  }
+  if (rc != PTK_OK) return rc;
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, nq);
+  return PTK_OK;
+}
+
 template <int OVF, class M = ptk::MetricL2>
 int launch_radius_nd(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, float e, bool fill,
                      uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s,
@@ -111,6 +158,32 @@ int knn_nd(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t n
   int rc = PTK_OK;
   PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_nd<OVF, M>(t, d_q, perm, nq, k, e, d_out, s, no_register_list))));
   return rc;
+}
+
+int knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
+                  float radius, ptk::Neighbor* d_out, hipStream_t s) {
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_nd_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
+  return rc;
+}
+
+// knn_nd_deep for search_knn_within: unseeded, masked at `radius` when the row is stored.
+int knn_nd_within_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
+                       ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  const size_t smem = (size_t)16 * 64 * 8 + (size_t)t->dim * 64 * 8;
+  if (smem > t->lds_per_block)
+    return fail(PTK_ERR_UNSUPPORTED, "dimension %u does not fit the LDS staging of the device search", t->dim);
+  int rc = PTK_OK;
+  PTK_WITH_METRIC({
+    rc = allow_lds(ptk::knn_nd_within_kernel<16, -1, false, M>, smem);
+    if (rc == PTK_OK)
+      hipLaunchKernelGGL((ptk::knn_nd_within_kernel<16, -1, false, M>), dim3(blocks), dim3(64), smem, s, dev, d_q, nullptr,
+                         n, k, d_out, 3.402823466e+38f, radius);
+  });
+  if (rc != PTK_OK) return rc;
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
 }
 
 int knn_nd_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float e,

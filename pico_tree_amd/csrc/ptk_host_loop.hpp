@@ -162,6 +162,43 @@ int ptk_host_search_knn(const ptk_tree* t, const float* points, const float* q, 
   return PTK_OK;
 }
 
+// The results contract of search_knn_within (ptk.h) as it is written: the reference's search_knn row of min(k, n_points)
+// entries, the entries not below the radius dropped, the row padded with {-1, radius}.
+int ptk_host_search_knn_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint32_t k,
+                               float radius, ptk_neighbor* out) {
+  if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || out == nullptr)))
+    return fail(PTK_ERR_INVALID, "null argument");
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    auto* rows = reinterpret_cast<neighbor_t*>(out);
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, t->n_points);
+    rows_loop(nq, [&](uint64_t i) {
+      neighbor_t* b = rows + i * k;
+      std::vector<neighbor_t> full(kk);
+      internal::knn_visitor<neighbor_t*> v(full.data(), full.data() + kk);
+      search_one(t, flat, view, q + i * t->dim, v);
+      uint32_t n = 0;
+      while (n < kk && full[n].distance < radius) {
+        b[n] = full[n];
+        ++n;
+      }
+      for (; n < k; ++n) b[n] = neighbor_t{-1, radius};
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 int ptk_host_search_radius(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius, float e,
                            int sort, uint64_t* offsets, ptk_neighbor** out) {
   if (t == nullptr || points == nullptr || offsets == nullptr || out == nullptr || (nq > 0 && q == nullptr))

@@ -305,6 +305,27 @@ struct Knn64RegPolicy {
       worst = w;
     }
   }
+  // search_knn_within: slots start at the pruning bound `s` with index -1; when the search ends, every
+  // slot still holding the seed or a distance not below the radius is the pad {-1, radius}.
+  __device__ __forceinline__ void seed(double s) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      if ((uint32_t)j < k) {
+        ld[j] = s;
+        li[j] = -1;
+      }
+    }
+    worst = s;
+  }
+  __device__ __forceinline__ void mask(double radius) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      if ((uint32_t)j < k && (li[j] < 0 || !(ld[j] < radius))) {
+        ld[j] = radius;
+        li[j] = -1;
+      }
+    }
+  }
   __device__ __forceinline__ void store(Neighbor64* row) const {
 #pragma unroll
     for (int j = 0; j < K; ++j) {
@@ -777,6 +798,50 @@ __global__ __launch_bounds__(64) void knn64_reg_kernel(
   Knn64RegPolicy<K> pol;
   pol.init(k, e_inv);
   search64<M, D3>(t, queries, qi, pol, stack, slots);
+  pol.store(out + qi * k);
+}
+
+// search_knn_within, k > 64: knn64_kernel's list seeded at `seed` (DBL_MAX: unseeded), the row stored
+// with every entry not below `radius` -- and every slot never filled -- as the pad {-1, radius}.
+template <class M, bool D3>
+__global__ __launch_bounds__(64) void knn64_within_kernel(
+    DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,
+    uint32_t k, Neighbor64* __restrict__ out, Rec64* __restrict__ stack, uint32_t slots, double seed, double radius) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  Knn64Policy pol;
+  pol.list = out + qi * k;
+  pol.k = k;
+  pol.filled = 0;
+  pol.worst = seed;
+  pol.e_inv = 1.0;
+  search64<M, D3>(t, queries, qi, pol, stack, slots);
+  for (uint32_t j = 0; j < k; ++j) {
+    Neighbor64 nb;
+    if (j < pol.filled) nb = pol.list[j];
+    if (j >= pol.filled || !(nb.distance < radius)) {
+      nb.index = -1;
+      nb.pad_ = 0;
+      nb.distance = radius;
+    }
+    pol.list[j] = nb;
+  }
+}
+
+// search_knn_within, k <= K <= 64, any k against n_points (an unfilled slot is the pad).
+template <class M, int K, bool D3>
+__global__ __launch_bounds__(64) void knn64_reg_within_kernel(
+    DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,
+    uint32_t k, Neighbor64* __restrict__ out, Rec64* __restrict__ stack, uint32_t slots, double seed, double radius) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  Knn64RegPolicy<K> pol;
+  pol.init(k, 1.0);
+  pol.seed(seed);
+  search64<M, D3>(t, queries, qi, pol, stack, slots);
+  pol.mask(radius);
   pol.store(out + qi * k);
 }
 
