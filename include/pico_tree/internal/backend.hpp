@@ -209,6 +209,10 @@ struct ptk_api<float> {
   static int knn_within(tree const* t, float const* q, std::uint64_t nq, std::uint32_t k, float r, neighbor* out) {
     return ptk_search_knn_within(t, q, nq, k, r, out);
   }
+  static int count_within(tree const* t, float const* q, std::uint64_t nq, float r, std::uint64_t max_count,
+                          std::uint64_t* counts) {
+    return ptk_search_count_within(t, q, nq, r, max_count, counts);
+  }
   static int radius(tree const* t, float const* q, std::uint64_t nq, float r, float e, int sort,
                     std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius(t, q, nq, r, e, sort, offsets, out);
@@ -229,6 +233,10 @@ struct ptk_api<double> {
   }
   static int knn_within(tree const* t, double const* q, std::uint64_t nq, std::uint32_t k, double r, neighbor* out) {
     return ptk_search64_knn_within(t, q, nq, k, r, out);
+  }
+  static int count_within(tree const* t, double const* q, std::uint64_t nq, double r, std::uint64_t max_count,
+                          std::uint64_t* counts) {
+    return ptk_search64_count_within(t, q, nq, r, max_count, counts);
   }
   static int radius(tree const* t, double const* q, std::uint64_t nq, double r, double e, int sort,
                     std::uint64_t* offsets, neighbor** out) {

@@ -145,4 +145,31 @@ class radius_visitor {
   std::vector<neighbor_type>& out_;
 };
 
+//! \brief The radius visitor counting instead of pushing: the number of points the
+//! search visits with a distance below the radius (strict, as radius_visitor).
+//! With \p max_count > 0, count() reports at most max_count (the search itself
+//! still visits what the radius search visits).
+template <typename Scalar_>
+class count_visitor {
+ public:
+  using scalar_type = Scalar_;
+
+  count_visitor(scalar_type radius, std::size_t max_count = 0)
+      : radius_(radius), limit_(max_count) {}
+
+  template <typename Index_>
+  void operator()(Index_, scalar_type dst) {
+    if (max() > dst) ++count_;
+  }
+  scalar_type max() const { return radius_; }
+  std::size_t count() const {
+    return limit_ != 0 && count_ > limit_ ? limit_ : count_;
+  }
+
+ private:
+  scalar_type radius_;
+  std::size_t limit_;
+  std::size_t count_ = 0;
+};
+
 }  // namespace pico_tree::internal

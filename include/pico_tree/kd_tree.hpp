@@ -217,6 +217,16 @@ class kd_tree {
     search_knn(x, e, knn.begin(), knn.end());
   }
 
+  //! The number of points with distance < \p radius (metric units: squared
+  //! for the default metric): the length of search_radius(x, radius)'s row,
+  //! counted by the radius visitor without the row.  Any metric.
+  template <typename P_>
+  inline size_type count_within(P_ const& x, scalar_type const radius) const {
+    internal::count_visitor<scalar_type> v(radius);
+    search_nearest(x, v);
+    return static_cast<size_type>(v.count());
+  }
+
   //! All points with distance < \p radius (metric units: squared for the
   //! default metric), in traversal order unless \p sort.
   template <typename P_>
@@ -302,6 +312,17 @@ class kd_tree {
       scalar_type const radius,
       neighbor_type* out) const {
     batched_knn_within(queries, k, radius, out);
+  }
+
+  //! counts[i] = count_within(query i, radius), clamped to \p max_count when
+  //! that is > 0.  \p radius must be >= 0 and not NaN.
+  template <typename QuerySpace_>
+  inline void count_within(
+      QuerySpace_ const& queries,
+      scalar_type const radius,
+      size_type* counts,
+      size_type const max_count = 0) const {
+    batched_count_within(queries, radius, counts, max_count);
   }
 
   //! out[i] = all neighbours of query i within \p radius.
@@ -527,6 +548,30 @@ class kd_tree {
         search_knn_within(x, k, radius, row);
         std::copy(row.begin(), row.end(), out + i * k);
         std::fill(out + i * k + row.size(), out + (i + 1) * k, neighbor_type(index_type(-1), radius));
+      });
+    }
+  }
+
+  template <typename QuerySpace_>
+  void batched_count_within(
+      QuerySpace_ const& queries, scalar_type radius, size_type* counts, size_type max_count) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    std::vector<std::uint64_t> c(q.rows());
+    try {
+      internal::ptk_check(
+          api::count_within(device(), q.data(), q.rows(), radius, static_cast<std::uint64_t>(max_count), c.data()),
+          "ptk_search_count_within");
+      std::copy(c.begin(), c.end(), counts);
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(q.rows(), [&](size_type i) {
+        row_point x = make_row(q.data() + i * q.cols(), q.cols());
+        size_type const n = count_within(x, radius);
+        counts[i] = max_count != 0 && n > max_count ? max_count : n;
       });
     }
   }

@@ -237,6 +237,23 @@ int ptk_search_knn_within_device(const ptk_tree* tree, const float* d_queries,
                                  uint64_t nq, uint32_t k, float radius,
                                  ptk_neighbor* d_out, void* stream);
 
+/* ---- neighbour counts within a radius ------------------------------------ */
+
+/* Results contract: counts[i] is the length of the reference's search_radius(q_i, radius) row -- the
+ * points its traversal visits with distance < radius (strict: search_visitor.hpp:141) -- and, with max_count > 0,
+ * min(that length, max_count); max_count == 0 means no limit.  radius is in metric units (squared for L2^2); 0 gives
+ * zeros, FLT_MAX and +inf are valid; NaN or a negative radius is PTK_ERR_INVALID, as is a null `counts` with nq > 0.
+ * Exact (no e).  A query row with NaN or +-Inf coordinates gets what the reference gives it.  Every metric; what the
+ * device refuses is PTK_ERR_UNSUPPORTED (ptk_host_search_count_within serves it).  The rows are never built, and the
+ * handle's radius capture (ptk_search_radius_count / _fill) is left as it is.  The first call on a handle builds a
+ * per-branch side table on the device (ptk_tree_info.device_bytes includes it from then on); the device form
+ * otherwise only enqueues on `stream`, as ptk_search_knn_device.  The host form moves the batch through the handle's
+ * device buffers. */
+int ptk_search_count_within(const ptk_tree* tree, const float* queries, uint64_t nq, float radius,
+                            uint64_t max_count, uint64_t* counts);
+int ptk_search_count_within_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, float radius,
+                                   uint64_t max_count, uint64_t* d_counts, void* stream);
+
 /* ---- radius search (ragged output) ------------------------------------ */
 
 /* Pass 1: counts[i] = number of points with distance < radius (strict,
@@ -304,6 +321,8 @@ int ptk_host_search_knn(const ptk_tree* tree, const float* points, const float* 
                         float e, ptk_neighbor* out);
 int ptk_host_search_knn_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
                                uint32_t k, float radius, ptk_neighbor* out);
+int ptk_host_search_count_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
+                                 float radius, uint64_t max_count, uint64_t* counts);
 int ptk_host_search_radius(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
                            float e, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
@@ -383,6 +402,11 @@ int ptk_search64_knn_within(const ptk_tree64* tree, const double* queries, uint6
 int ptk_search64_knn_within_device(const ptk_tree64* tree, const double* d_queries,
                                    uint64_t nq, uint32_t k, double radius,
                                    ptk_neighbor64* d_out, void* stream);
+/* As ptk_search_count_within / ptk_search_count_within_device. */
+int ptk_search64_count_within(const ptk_tree64* tree, const double* queries, uint64_t nq, double radius,
+                              uint64_t max_count, uint64_t* counts);
+int ptk_search64_count_within_device(const ptk_tree64* tree, const double* d_queries, uint64_t nq, double radius,
+                                     uint64_t max_count, uint64_t* d_counts, void* stream);
 /* As ptk_search_radius: *out is malloc'ed by the library (ptk_free).  With
  * sort != 0 rows ascend by distance, equal distances by index. */
 int ptk_search64_radius(const ptk_tree64* tree, const double* queries,

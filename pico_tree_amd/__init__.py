@@ -98,6 +98,8 @@ _SIGNATURES = {
                                       c_void_p]),
     "ptk_search_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_search_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p]),
+    "ptk_search_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
+    "ptk_search_count_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_count": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p]),
     "ptk_search_radius_fill": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p,
                                        c_void_p, c_int]),
@@ -114,6 +116,7 @@ _SIGNATURES = {
     "ptk_free": (None, [c_void_p]),
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
+    "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
     "ptk_host_search_radius": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_float, c_int,
                                        c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -135,6 +138,8 @@ _SIGNATURES = {
     "ptk_search64_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
     "ptk_search64_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
+    "ptk_search64_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p]),
+    "ptk_search64_count_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_radius": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_double, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "ptk_search64_box": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -860,6 +865,40 @@ class KdTree:
         if rows is not nns:
             nns.reshape(-1)[:] = rows.reshape(-1)
         return nns
+
+    def count_within(self, pts, radius: float, max_count: int = 0):
+        """``count_within(pts, radius, max_count=0)`` -- how many points lie closer than ``radius`` to each query.
+
+        ``counts[i]`` is the length of :meth:`search_radius`'s row i (distance ``< radius``, metric units: squared for
+        L2 squared), clamped to ``max_count`` when that is > 0 (``ptk_search_count_within`` /
+        ``ptk_search64_count_within``).  Exact; the rows are never built.  Host arrays (row- or column-major, the
+        tree's dtype) give an ``int64[nq]`` array; a torch CUDA tensor gives an ``int64`` tensor on its device, enqueued
+        on the current stream.
+        """
+        r = self._real(radius)
+        max_count = int(max_count)
+        if max_count < 0:
+            raise ValueError("max_count must be >= 0")
+        if _is_torch(pts):
+            import torch
+            tq = torch.float64 if self._f64 else torch.float32
+            if pts.dtype != tq or pts.dim() != 2 or pts.shape[1] != self._sdim:
+                raise ValueError(f"queries must be a {self._dtype.name} (nq, sdim) tensor")
+            if not pts.is_cuda or not pts.is_contiguous():
+                raise ValueError("queries must be a contiguous CUDA tensor")
+            nq = pts.shape[0]
+            out = torch.empty((nq,), dtype=torch.int64, device=pts.device)
+            stream = torch.cuda.current_stream(pts.device).cuda_stream
+            _check(self._fn("ptk_search_count_within_device")(self._h, pts.data_ptr(), nq, r, max_count, out.data_ptr(),
+                                                             stream))
+            return out
+        q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
+        nq = q.shape[0]
+        counts = np.zeros((nq,), dtype=np.int64)
+        self._served(self._fn("ptk_search_count_within")(self._h, q.ctypes.data, nq, r, max_count, counts.ctypes.data),
+                     lambda lib: lib.ptk_host_search_count_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq,
+                                                                  np.float32(radius), max_count, counts.ctypes.data))
+        return counts
 
     def _served(self, status: int, host_loop) -> None:
         """``_check``: every failure raises.  Only after ``allow_host_loop(True)`` is a search the DEVICE refuses for a

@@ -216,6 +216,7 @@ int upload(ptk_tree& t, const float* points) {
   t.dev.cbits = enc.cbits;
   t.dev.cmask = (1u << enc.cbits) - 1u;
   t.dev.n_points = (uint32_t)t.n_points;
+  t.n_branches = enc.nodes.size();
   t.gpu_layout = true;
   // Piles -- subtrees of one point many times over: the k = 1 search gets a view in which each is a leaf of one point
   // (ptk_piles.hpp).  A tree of points in general position pays one pass over its branch records here.
@@ -292,6 +293,7 @@ struct ProcessWarmup {
       ptkf::warm_radius();
       ptkf::warm_nd();
       ptkf::warm_topo();
+      ptkf::warm_count();
       ptkf::warm_f64();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
@@ -1127,6 +1129,7 @@ void ptk_tree_destroy(ptk_tree* t) {
     if (t->d_ranges1) (void)hipFree(t->d_ranges1);
     if (t->d_pile_of_point) (void)hipFree(t->d_pile_of_point);
     if (t->d_pile_recs) (void)hipFree(t->d_pile_recs);
+    if (t->d_count_table) (void)hipFree(t->d_count_table);
   }
   delete t;
 }
@@ -1848,6 +1851,120 @@ int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32
     return rc;
   }
   PTK_HIP(hipMemcpyAsync(out, io.d_out, (size_t)nq * row_out, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  return PTK_OK;
+}
+
+// ---- neighbour counts within a radius ---------------------------------------
+
+// The side table of count_within_kernel: built once per handle, on the first count, under the handle's own lock (calls
+// that arrive together wait for the one that builds it).
+static int count_table_of(const ptk_tree* t, hipStream_t s) {
+  std::lock_guard<std::mutex> lock(t->count_table_mutex);
+  if (t->count_table_built) return PTK_OK;
+  void* table = nullptr;
+  const int rc = ptkf::count_table(t, &table, s);
+  if (rc != PTK_OK) return rc;
+  ptk_tree* m = const_cast<ptk_tree*>(t);
+  m->d_count_table = table;
+  m->device_bytes += t->n_branches * ptkf::kCountBoxBytes;
+  m->count_table_built = true;
+  return PTK_OK;
+}
+
+// count_within never goes through radius_pass_device: the handle's radius capture (Workspace::cap_*) stays as the last
+// count pass left it.  3-D trees of the four non-topological metrics take count_within_kernel (the clamp in the kernel);
+// dim > 3, the topological metrics and deep trees the count kernels of the radius search, clamped afterwards.
+int ptk_search_count_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, uint64_t max_count,
+                                   uint64_t* d_counts, void* stream) {
+  int rc = check_search(t, d_q, nq);
+  if (rc != PTK_OK) return rc;
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (d_counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const bool nd = t->dim > 3;
+  if (!nd && !topological(t) && !deep_tree(t)) {
+    rc = count_table_of(t, s);
+    if (rc != PTK_OK) return rc;
+  }
+  const bool reorder = want_reorder(t, nq);
+  Scratch scratch(t, s, /*per_stream=*/true);
+  if (topological(t)) {
+    if (deep_tree(t)) return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
+    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+    if (rc != PTK_OK) return rc;
+    uint32_t* perm = nullptr;
+    if (reorder) {
+      rc = make_permutation(t, d_q, nq, s, scratch, &perm);
+      if (rc != PTK_OK) return rc;
+    }
+    rc = ptkf::radius_topo(t, d_q, perm, nq, radius, 1.0f, false, d_counts, nullptr, nullptr, s);
+  } else if (deep_tree(t)) {  // record stacks spilling to HBM, a few queries per launch
+    const DeepPlan plan = deep_plan(t, nq);
+    rc = scratch.reserve(plan.bytes());
+    if (rc != PTK_OK) return rc;
+    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
+    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
+    Timer timer(t, s);
+    for (uint64_t lo = 0; lo < nq && rc == PTK_OK; lo += plan.piece) {
+      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
+      if (nd) {
+        ptk::DevTreeND dev = t->dev_nd;
+        dev.deep_spill = spill;
+        dev.deep_cap = plan.cap;
+        rc = ptkf::radius_nd_deep(t, dev, d_q + lo * t->dim, n, radius, 1.0f, false, d_counts + lo, nullptr, nullptr, s);
+      } else {
+        ptk::DevTree dev = t->dev;
+        dev.deep_spill = spill;
+        dev.deep_cap = plan.cap;
+        rc = ptkf::radius_deep(t, dev, d_q + lo * t->dim, n, radius, 1.0f, false, d_counts + lo, nullptr, nullptr, s);
+      }
+    }
+    timer.stop(0, nq);
+  } else {
+    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+    if (rc != PTK_OK) return rc;
+    uint32_t* perm = nullptr;
+    if (reorder) {  // (the batch order of the radius count pass: a query costs what it finds, the densest cells first)
+      rc = make_permutation(t, d_q, nq, s, scratch, &perm, nd ? 0u : ptk::kCellsDenseFirst);
+      if (rc != PTK_OK) return rc;
+    }
+    if (!nd)
+      return ptkf::count_within(t, d_q, perm, nq, radius, max_count, knob_int("count_shortcut", 1) != 0, d_counts, s);
+    rc = ptkf::radius_nd(t, d_q, nq, radius, 1.0f, false, d_counts, nullptr, nullptr, s, perm);
+  }
+  if (rc != PTK_OK) return rc;
+  return ptkf::clamp_counts(d_counts, nq, max_count, s);
+}
+
+// Host buffers: the batch goes up, is counted on one stream of the handle and comes down, under the handle's I/O lock.
+int ptk_search_count_within(const ptk_tree* t, const float* q, uint64_t nq, float radius, uint64_t max_count,
+                            uint64_t* counts) {
+  int rc = check_search(t, q, nq);
+  if (rc != PTK_OK) return rc;
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t row_in = (size_t)t->dim * sizeof(float);
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  rc = grow_device_block(&io.d_in, &io.in_capacity, (size_t)nq * row_in);
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, (size_t)nq * sizeof(uint64_t));
+  if (rc != PTK_OK) return rc;
+  PTK_HIP(hipMemcpyAsync(io.d_in, q, (size_t)nq * row_in, hipMemcpyHostToDevice, io.search[0]));
+  rc = ptk_search_count_within_device(t, reinterpret_cast<const float*>(io.d_in), nq, radius, max_count,
+                                      reinterpret_cast<uint64_t*>(io.d_out), io.search[0]);
+  if (rc != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return rc;
+  }
+  PTK_HIP(hipMemcpyAsync(counts, io.d_out, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, io.search[0]));
   PTK_HIP(hipStreamSynchronize(io.search[0]));
   return PTK_OK;
 }

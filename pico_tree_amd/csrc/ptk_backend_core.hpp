@@ -217,8 +217,13 @@ struct ptk_tree {
   void* d_cells = nullptr;  // dim <= 3: which cells of a coarse Morton grid hold tree points (ptk::CellTable)
   ptk::CellTable cells{};
   ptk::DevTreeND dev_nd{};
-  uint64_t device_bytes = 0;
+  std::atomic<uint64_t> device_bytes{0};  // (atomic: the count table adds to it while ptk_tree_get_info may read it)
   bool gpu_layout = false;
+  uint64_t n_branches = 0;  // dim <= 3: branch records of `dev`
+  // count_within (ptk_kernels_count.hpp): the per-branch side table {size, box}, built on the first count and kept.
+  void* d_count_table = nullptr;
+  bool count_table_built = false;
+  mutable std::mutex count_table_mutex;
 
   std::atomic<int> reorder{PTK_REORDER_AUTO};
   std::atomic<int> metric{PTK_METRIC_L2_SQUARED};

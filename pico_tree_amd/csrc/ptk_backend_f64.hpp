@@ -33,8 +33,13 @@ struct ptk_tree64 {
   void* d_outer = nullptr; // topological metrics only: double2 per branch (made by ptk_tree64_set_metric)
   void* d_occ = nullptr;   // which cells of the coarse Morton grid hold tree points (morton64_kernel): k-NN batches start
                            // their long searches first
-  uint64_t device_bytes = 0;
+  std::atomic<uint64_t> device_bytes{0};  // (atomic: the count table adds to it while ptk_tree64_get_info may read it)
   uint32_t slots = 0;      // stack records a lane may need: 2 * depth + 4
+  uint64_t n_branches = 0;
+  // count_within (ptk_kernels_count64.hpp): the per-branch side table, built on the first count of a dim <= 3 tree.
+  void* d_count_table = nullptr;
+  bool count_table_built = false;
+  mutable std::mutex count_table_mutex;
   int cus = 256;           // compute units of the device
   // counters of the last capped k-NN call (ptk_tree64_debug_knn_counts): they live in the stack block
   mutable uint32_t* last_meta = nullptr;
@@ -123,6 +128,7 @@ int encode64(ptk_tree64& t, const double* points) {
   }
   t.device_bytes = nb + pb + ib + rb + bb + (size_t(1) << ptk::kMorton64CellBits);
   t.dev.nodes = static_cast<const ptk::Node64*>(t.d_nodes);
+  t.n_branches = enc.nodes.size();
   t.dev.pts = static_cast<const double*>(t.d_pts);
   t.dev.index = static_cast<const int32_t*>(t.d_index);
   t.dev.ranges = static_cast<const uint2*>(t.d_ranges);
@@ -832,6 +838,7 @@ void ptk_tree64_destroy(ptk_tree64* t) {
     if (t->d_root) (void)hipFree(t->d_root);
     if (t->d_outer) (void)hipFree(t->d_outer);
     if (t->d_occ) (void)hipFree(t->d_occ);
+    if (t->d_count_table) (void)hipFree(t->d_count_table);
     for (char* b : t->io)
       if (b) (void)hipFree(b);
   }
@@ -981,6 +988,83 @@ int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, u
   if (he == hipSuccess) {
     rc = ptk_search64_knn_within_device(t, d_q, nq, k, radius, d_out, nullptr);
     if (rc == PTK_OK) he = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  return rc;
+}
+
+// count_within (ptk.h): dim <= 3 and the four non-topological metrics take count64_within_kernel (the
+// clamp in the kernel; the side table built by the first call); other trees the count pass of the radius search
+// (radius64_kernel, no capture), clamped to max_count on the device.
+static int count_table64_of(const ptk_tree64* t, hipStream_t s) {
+  std::lock_guard<std::mutex> lock(t->count_table_mutex);
+  if (t->count_table_built) return PTK_OK;
+  void* table = nullptr;
+  const int rc = ptkf::count_table64(t->dev, t->n_branches, &table, s);
+  if (rc != PTK_OK) return rc;
+  ptk_tree64* m = const_cast<ptk_tree64*>(t);
+  m->d_count_table = table;
+  m->device_bytes += t->n_branches * ptkf::kCountBox64Bytes;
+  m->count_table_built = true;
+  return PTK_OK;
+}
+
+int ptk_search64_count_within_device(const ptk_tree64* t, const double* d_q, uint64_t nq, double radius, uint64_t max_count,
+                                     uint64_t* d_counts, void* stream) {
+  int rc = check_search64(t, d_q, nq);
+  if (rc != PTK_OK) return rc;
+  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (d_counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const int m = t->metric.load();
+  const bool own = t->dim <= 3 && m != PTK_METRIC_SO2 && m != PTK_METRIC_SE2_SQUARED;
+  if (own) {
+    rc = count_table64_of(t, s);
+    if (rc != PTK_OK) return rc;
+  }
+  Stack64Lease lease(t, s);
+  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
+  rc = lease.acquire(nq, perm_bytes);
+  if (rc != PTK_OK) return rc;
+  const uint32_t* perm = nullptr;
+  rc = make_permutation64(t, d_q, nq, s, lease, &perm);
+  if (rc != PTK_OK) return rc;
+  if (own) {
+    const bool shortcut = knob_int("count_shortcut", 1) != 0;
+    for (uint64_t q0 = 0; q0 < nq && rc == PTK_OK; q0 += lease.piece)
+      rc = ptkf::count64_within(t->dev, t->metric.load(), static_cast<const ptk::CountBox64*>(t->d_count_table), d_q, perm,
+                                q0, std::min(lease.piece, nq - q0), radius, max_count, shortcut, d_counts, lease.stack,
+                                t->slots, s);
+    return rc;
+  }
+  PTK_WITH_METRIC64(rc = (launch_radius64<M, false>(t, d_q, perm, nq, radius, 1.0, d_counts, nullptr, nullptr, s, lease)));
+  if (rc != PTK_OK) return rc;
+  return ptkf::clamp_counts(d_counts, nq, max_count, s);
+}
+
+int ptk_search64_count_within(const ptk_tree64* t, const double* q, uint64_t nq, double radius, uint64_t max_count,
+                              uint64_t* counts) {
+  int rc = check_search64(t, q, nq);
+  if (rc != PTK_OK) return rc;
+  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  if (nq == 0) return PTK_OK;
+  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bq, bc;
+  const size_t qbytes = (size_t)nq * t->dim * sizeof(double), cbytes = (size_t)nq * sizeof(uint64_t);
+  hipError_t he = bq.get(t, 0, qbytes);
+  if (he == hipSuccess) he = bc.get(t, 1, cbytes);
+  double* d_q = reinterpret_cast<double*>(bq.p);
+  uint64_t* d_c = reinterpret_cast<uint64_t*>(bc.p);
+  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    rc = ptk_search64_count_within_device(t, d_q, nq, radius, max_count, d_c, nullptr);
+    if (rc == PTK_OK) he = hipMemcpy(counts, d_c, cbytes, hipMemcpyDeviceToHost);
   }
   if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return rc;

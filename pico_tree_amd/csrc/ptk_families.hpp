@@ -5,6 +5,12 @@
 
 #include "ptk_backend_core.hpp"
 
+namespace ptk {
+struct DevTree64;
+struct CountBox64;
+struct Rec64;
+}  // namespace ptk
+
 namespace ptkf {
 // ptk_backend.hip: the batch order (the library's radix sort of 32-bit keys; rocprim is compiled into that unit only)
 int morton_bits(uint64_t nq);
@@ -68,6 +74,19 @@ int knn_topo(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t
 int radius_topo(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e, bool fill,
                 uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s);
 void warm_topo();
+// ptk_family_count.hip: count_within of 3-D float32 trees (ptk_kernels_count.hpp); the side table holds kCountBoxBytes per branch
+constexpr size_t kCountBoxBytes = 32;
+int count_table(const ptk_tree* t, void** d_table, hipStream_t s);
+int count_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, uint64_t max_count,
+                 bool shortcut, uint64_t* d_counts, hipStream_t s);
+int clamp_counts(uint64_t* d_counts, uint64_t n, uint64_t max_count, hipStream_t s);
+// ... and of float64 trees with dim <= 3 (ptk_kernels_count64.hpp): kCountBox64Bytes per branch
+constexpr size_t kCountBox64Bytes = 64;
+int count_table64(const ptk::DevTree64& dev, uint64_t n_branches, void** d_table, hipStream_t s);
+int count64_within(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, const double* d_q,
+                   const uint32_t* perm, uint64_t q0, uint64_t n, double radius, uint64_t max_count, bool shortcut,
+                   uint64_t* d_counts, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
+void warm_count();
 // ptk_family_f64.hip
 void warm_f64();
 }  // namespace ptkf

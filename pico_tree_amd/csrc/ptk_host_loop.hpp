@@ -199,6 +199,32 @@ int ptk_host_search_knn_within(const ptk_tree* t, const float* points, const flo
   return PTK_OK;
 }
 
+// count_within (ptk.h) as it is written: the reference's radius search of each row, counting instead of pushing.
+int ptk_host_search_count_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius,
+                                 uint64_t max_count, uint64_t* counts) {
+  if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || counts == nullptr)))
+    return fail(PTK_ERR_INVALID, "null argument");
+  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    rows_loop(nq, [&](uint64_t i) {
+      internal::count_visitor<float> v(radius, (std::size_t)max_count);
+      search_one(t, flat, view, q + i * t->dim, v);
+      counts[i] = v.count();
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 int ptk_host_search_radius(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius, float e,
                            int sort, uint64_t* offsets, ptk_neighbor** out) {
   if (t == nullptr || points == nullptr || offsets == nullptr || out == nullptr || (nq > 0 && q == nullptr))
