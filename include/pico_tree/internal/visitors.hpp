@@ -109,6 +109,10 @@ class knn_visitor {
     }
   }
   scalar_type max() const { return (end_ - 1)->distance; }
+  //! One past the last entry the search has written (end once the list is
+  //! full); with fewer accepted points than slots, [filled(), end - 1) is as
+  //! the caller left it, as in the reference.
+  RandomAccessIterator_ filled() const { return filled_; }
 
  private:
   candidate_scale<scalar_type, Approximate_> scale_;

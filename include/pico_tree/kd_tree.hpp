@@ -187,8 +187,11 @@ class kd_tree {
       std::fill(knn.begin(), knn.end(), neighbor_type(index_type(-1), seed));
     }
     search_nearest(x, v);
+    // (only the entries the search wrote: a query no distance is below the largest scalar from -- NaN, +-Inf --
+    // accepts nothing, and the slots of an unseeded list are then as resize() left them)
+    size_type const found = static_cast<size_type>(v.filled() - knn.begin());
     size_type n = 0;
-    while (n < knn.size() && knn[n].index != index_type(-1) && knn[n].distance < radius) ++n;
+    while (n < found && knn[n].index != index_type(-1) && knn[n].distance < radius) ++n;
     knn.resize(n);
   }
 

@@ -40,6 +40,35 @@
  * kd_tree on the same inputs, squared distances bit-identical to the reference
  * compiled without FMA contraction (-ffp-contract=off).
  *
+ * Non-finite and overflowing inputs (tests/test_non_finite.py):
+ *   - A query row or a box corner may hold NaN, +-Inf or any finite value, a
+ *     value whose distances overflow included.  Such a row gets what the
+ *     reference gives it, in every search (knn, knn_within, count_within,
+ *     radius, box; float32 and float64; every metric), for every entry the
+ *     reference writes; no query row changes the result of another row; and
+ *     the call returns PTK_OK.  (A row with a NaN or an infinite coordinate
+ *     accepts no point under the sum metrics: `max > distance` is false.  A
+ *     NaN box corner coordinate does not bound its side of the axis:
+ *     box.hpp:31-40 tests `min > x || max < x`; under the two topological
+ *     metrics the reference's query box is a metric_box_map, which tests
+ *     `min <= x && x <= max` (segment.hpp:32,63): there it contains nothing.)
+ *   - A k-NN slot the reference's search never writes -- k > n_points; a row
+ *     that accepts fewer than k points, where the reference writes the
+ *     distance of slot k - 1 only and leaves the rest of the caller's row as
+ *     it found it (search_visitor.hpp:50,102) -- holds {index 0, distance
+ *     FLT_MAX} ({0, DBL_MAX}, pad_ zero, for ptk_neighbor64) on every path:
+ *     every k, any dimension, every metric, device and ptk_host_search_knn.
+ *     No slot of an output row is left unwritten.  (search_knn_within keeps
+ *     its own padding, {-1, radius}.)
+ *   - The POINTS a tree is built from must be finite: ptk_tree_create_from_points,
+ *     ptk_tree64_create_from_points and ptk_multi_create_from_points return
+ *     PTK_ERR_INVALID, the message naming the first offending point, for a
+ *     NaN or +-Inf coordinate (the builder partitions with `<` through
+ *     std::nth_element as the reference's, kd_tree_builder.hpp: NaN makes that
+ *     undefined, an infinite coordinate makes a NaN split).  +-FLT_MAX is
+ *     finite and accepted.  The *_create_from_stream loaders and
+ *     ptk_tree_create do not look at the points, as the reference's load.
+ *
  * Threading: a ptk_tree is immutable after creation; search calls on one handle
  * may be issued concurrently from several host threads (each call uses its own
  * scratch; calls that share a HIP stream serialise on it).
@@ -138,7 +167,9 @@ int ptk_warmup(int32_t device);
 /* ---- tree lifetime ---------------------------------------------------- */
 
 /* Builds the kd-tree on the host (sliding midpoint, max_leaf_size stop, bounds
- * from the points) and uploads it.  points may be freed after the call. */
+ * from the points) and uploads it.  points may be freed after the call.  A point
+ * with a NaN or +-Inf coordinate: PTK_ERR_INVALID, no handle ("Non-finite and
+ * overflowing inputs" above). */
 int ptk_tree_create_from_points(const float* points, uint64_t n_points,
                                 uint32_t dim, uint64_t max_leaf_size,
                                 int32_t device, ptk_tree** out);
@@ -206,9 +237,11 @@ int ptk_tree_create_from_topological_stream(const float* points, uint64_t n_poin
 /* ---- k nearest neighbours --------------------------------------------- */
 
 /* Host buffers.  queries: nq x dim row-major.  out: nq x k row-major; row i is
- * the ascending k-list of query i.  k is clamped by the CALLER to <= n_points
- * (kd_tree.hpp:193); k > n_points is PTK_ERR_INVALID.  e is the approximation
- * ratio in metric units (kd_tree.hpp:131-153); e == 1 is the exact search. */
+ * the ascending k-list of query i.  k > n_points, or a query row that accepts
+ * fewer than k points (NaN, +-Inf, distances that overflow): the accepted
+ * neighbours in order, then {0, FLT_MAX} in every slot behind them ("Non-finite
+ * and overflowing inputs" above).  e is the approximation ratio in metric units
+ * (kd_tree.hpp:131-153); e == 1 is the exact search. */
 int ptk_search_knn(const ptk_tree* tree, const float* queries, uint64_t nq,
                    uint32_t k, float e, ptk_neighbor* out);
 

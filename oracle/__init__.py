@@ -173,9 +173,18 @@ class Oracle:
             raise ValueError("queries must be (nq, dim)")
         return q
 
-    def search_nn(self, q, e: float | None = None, counters: bool = False):
+    def _rows(self, out, shape):
+        """The result buffer of a k-NN call: a fresh one, or the caller's ``out`` (C-contiguous, of the result dtype and
+        shape), which the search then writes in place -- entries the search does not write keep what ``out`` held."""
+        if out is None:
+            return np.empty(shape, dtype=self.neighbor)
+        if out.dtype != self.neighbor or out.shape != shape or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError(f"out must be a writable C-contiguous {shape} array of the neighbor dtype")
+        return out
+
+    def search_nn(self, q, e: float | None = None, counters: bool = False, out=None):
         q = self._queries(q)
-        out = np.empty(len(q), dtype=self.neighbor)
+        out = self._rows(out, (len(q),))
         if self.kind == "port":
             cnt = np.zeros((len(q), 5), dtype=np.uint32) if counters else None
             self._fn("search_nn", None,
@@ -189,12 +198,12 @@ class Oracle:
             self._h, self._ptr(q), len(q), out.ctypes.data)
         return out
 
-    def search_knn(self, q, k: int, e: float | None = None, counters: bool = False):
+    def search_knn(self, q, k: int, e: float | None = None, counters: bool = False, out=None):
         q = self._queries(q)
         k = int(k)
         if k < 1 or k > self.n:
             raise ValueError("oracle requires 1 <= k <= n")
-        out = np.empty((len(q), k), dtype=self.neighbor)
+        out = self._rows(out, (len(q), k))
         if self.kind == "port":
             cnt = np.zeros((len(q), 5), dtype=np.uint32) if counters else None
             self._fn("search_knn", None,

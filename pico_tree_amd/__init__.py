@@ -548,6 +548,9 @@ class KdTree:
     float32 -> the tuned kernels (``ptk_*``), float64 -> the double-precision
     kernels (``ptk_tree64_*`` / ``ptk_search64_*``, results ``NEIGHBOR64``).  The tree
     is built on the host with the sliding-midpoint rule and uploaded once.
+
+    The points must be finite: a NaN or +-Inf coordinate raises :class:`PtkError` (``PTK_ERR_INVALID``, the message
+    names the first offending point); +-FLT_MAX is accepted.  ``load_kd_tree`` does not look at the points.
     """
 
     def __init__(self, pts, metric: Metric = Metric.L2Squared, max_leaf_size: int = 10,
@@ -781,6 +784,12 @@ class KdTree:
         Host arrays return (or fill) a numpy array of :data:`NEIGHBOR`; a torch
         CUDA tensor returns a :class:`DeviceNeighbors` (``nns`` may be a
         preallocated int32 ``(nq, k, 2)`` tensor).
+
+        A query row with NaN, +-Inf or any finite value (one whose distances overflow included) gets what the
+        reference gives it, for every entry the reference writes, and changes no other row.  A slot the reference's
+        search never writes -- ``k > npts``; a row that accepts fewer than ``k`` points (a NaN or +-Inf row accepts
+        none) -- holds ``(index 0, distance FLT_MAX)`` (``DBL_MAX`` for float64): no slot of the result is left
+        unwritten, whatever ``nns`` held.
         """
         e, nns = self._split_optional(args)
         k = int(k)
@@ -932,7 +941,11 @@ class KdTree:
 
     # -- radius ---------------------------------------------------------------------------
     def search_radius(self, pts, radius: float, *args, sort: bool = False):
-        """``search_radius(pts, radius[, e][, nns], sort=False)`` -> :class:`DArray`."""
+        """``search_radius(pts, radius[, e][, nns], sort=False)`` -> :class:`DArray`.
+
+        A query row with NaN, +-Inf or any finite value gets the row the reference gives it (a NaN or +-Inf row
+        under the sum metrics: an empty one -- ``radius > distance`` is false) and changes no other row; ``radius``
+        may be ``FLT_MAX`` or ``+inf``."""
         e, nns, sort = self._split_optional_radius(args, sort)
         q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
         nq = q.shape[0]
@@ -958,7 +971,11 @@ class KdTree:
 
         ``boxes`` is ``(2 * nbox, sdim)``: rows ``2 i`` and ``2 i + 1`` are the min and max corner
         of box ``i`` (``_pyco_tree/kd_tree.hpp:245-268``).  Row ``i`` of the result lists the points
-        inside the closed box in the reference's traversal order."""
+        inside the closed box in the reference's traversal order.
+
+        A corner with NaN, +-Inf or any finite value gets what the reference gives it: its test is
+        ``min > x or max < x -> outside`` (``box.hpp:31-40``), so a NaN corner coordinate does not bound its side of
+        the axis (it does not empty the box), and an inverted box is empty."""
         b = self._as_matrix(boxes, self._sdim, "boxes", self._dtype)
         if b.shape[0] % 2 != 0:
             raise ValueError("query min and max don't have equal size")

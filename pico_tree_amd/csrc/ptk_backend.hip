@@ -1019,6 +1019,7 @@ int ptk_tree_create_from_points(const float* points, uint64_t n_points, uint32_t
   if (dim == 0 || n_points == 0 || max_leaf_size == 0)
     return fail(PTK_ERR_INVALID, "dim, n_points and max_leaf_size must be positive");
   if (n_points >= (1ull << 31)) return fail(PTK_ERR_INVALID, "n_points must be < 2^31");
+  if (const int rc = check_points_finite(points, n_points, dim); rc != PTK_OK) return rc;
   ptk_tree* t = new (std::nothrow) ptk_tree;
   if (t == nullptr) return fail(PTK_ERR_NOMEM, "out of memory");
   g_warmup.start(device);
@@ -1318,8 +1319,8 @@ int ptk_search_knn_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint
   // k > n_points: what the reference's iterator-range search_knn does with a range longer than the
   // tree (search_visitor.hpp:95-110; its Python binding passes k through unclamped): the n_points
   // neighbours in order, the last slot's distance left at the FLT_MAX sentinel.  The slots in
-  // between are the caller's in the reference; here they are zeroed.  (The register k-list assumes
-  // every slot gets filled, so these rows take the list-in-the-row kernels.)
+  // between are the caller's in the reference; here they hold {0, FLT_MAX} as every slot a search did
+  // not write (ptk.h; KnnPolicy::end_query).  (These rows take the list-in-the-row kernels.)
   const bool short_tree = k > t->n_points;
   // Very large batches go through in pieces of at most 2^25 queries: the scratch of a piece stays
   // at a few GB and every 32-bit index in the kernels holds (PTK_MAX_BATCH shrinks it for tests).
@@ -1334,8 +1335,6 @@ int ptk_search_knn_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint
   }
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  // (on the tree's device, once per piece: a null stream is the null stream of THAT device)
-  if (short_tree) PTK_HIP(hipMemsetAsync(d_out, 0, (size_t)nq * k * sizeof(ptk_neighbor), s));
   const bool l2 = t->metric.load() == PTK_METRIC_L2_SQUARED;
   // k = 1 takes the two-phase search (phase 1, class order, capped phase 2, cooperative search) under the default metric
   // and under metric_l1 on a tree without piles: both are sums of per-axis terms, so the box distance the reference

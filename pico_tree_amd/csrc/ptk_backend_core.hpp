@@ -268,6 +268,34 @@ inline unsigned build_threads() {
   return hc == 0 ? 1u : (hc > 32u ? 32u : hc);
 }
 
+// The points a tree is BUILT from must be finite (ptk.h): the builder partitions with `<` through std::nth_element, as
+// the reference's (kd_tree_builder.hpp), which a NaN makes undefined, and an infinite coordinate makes a NaN split.
+// One read of the points on the build's threads, before anything is allocated for them; PTK_OK, or PTK_ERR_INVALID
+// naming the first offending point.  (x - x is 0 for every finite x and NaN for NaN and +-Inf.)
+template <typename Scalar_>
+inline int check_points_finite(const Scalar_* points, uint64_t n_points, uint32_t dim) {
+  std::atomic<uint64_t> first{n_points};
+  ptk::parallel_chunks((size_t)n_points, build_threads(), size_t(1) << 16, [&](size_t lo, size_t hi, unsigned) {
+    for (size_t i = lo; i < hi; ++i) {
+      const Scalar_* p = points + i * dim;
+      Scalar_ acc = 0;
+      for (uint32_t a = 0; a < dim; ++a) acc += p[a] - p[a];
+      if (!(acc == 0)) {  // (chunks are ascending runs: the first hit of a chunk is its lowest)
+        uint64_t seen = first.load();
+        while (i < seen && !first.compare_exchange_weak(seen, (uint64_t)i)) {
+        }
+        return;
+      }
+    }
+  });
+  const uint64_t i = first.load();
+  if (i == n_points) return PTK_OK;
+  uint32_t a = 0;
+  while (a + 1 < dim && std::isfinite(points[i * dim + a])) ++a;
+  return fail(PTK_ERR_INVALID, "point %llu is not finite (coordinate %u is %g): a tree is built from finite points only",
+              (unsigned long long)i, a, (double)points[i * dim + a]);
+}
+
 
 // ---- launch helpers ---------------------------------------------------------------
 

@@ -794,6 +794,7 @@ int ptk_tree64_create_from_points(const double* points, uint64_t n_points, uint3
   if (dim == 0 || n_points == 0 || max_leaf_size == 0)
     return fail(PTK_ERR_INVALID, "dim, n_points and max_leaf_size must be positive");
   if (n_points >= (1ull << 31)) return fail(PTK_ERR_INVALID, "n_points must be < 2^31");
+  if (const int rc = check_points_finite(points, n_points, dim); rc != PTK_OK) return rc;
   ptk_tree64* t = new (std::nothrow) ptk_tree64;
   if (t == nullptr) return fail(PTK_ERR_NOMEM, "out of memory");
   try {
@@ -906,9 +907,9 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   // k > n_points, as the float32 entry (ptk_search_knn_device): the n_points neighbours in order, the last
-  // slot's distance at the DBL_MAX sentinel (search_visitor.hpp:95-110), the slots in between zeroed.
+  // slot's distance at the DBL_MAX sentinel (search_visitor.hpp:95-110), the slots in between {0, DBL_MAX} as well
+  // (Knn64Policy::end_query).
   const bool short_tree = k > t->n_points;
-  if (short_tree) PTK_HIP(hipMemsetAsync(d_out, 0, (size_t)nq * k * sizeof(ptk_neighbor64), s));
   Stack64Lease lease(t, s);
   uint32_t cap = knn64_cap(t, e, nq, k, short_tree);
   const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);

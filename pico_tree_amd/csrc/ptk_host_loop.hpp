@@ -144,14 +144,21 @@ int ptk_host_search_knn(const ptk_tree* t, const float* points, const float* q, 
     space_t space(points, t->n_points, t->dim);
     view_t view(space);
     auto* rows = reinterpret_cast<neighbor_t*>(out);
+    // A slot the search did not write (k > n_points; a row no distance is below FLT_MAX from) holds {0, FLT_MAX}, as
+    // the device rows (ptk.h): the visitor itself writes the distance of slot k - 1 only, as the reference's.
+    auto fill = [](neighbor_t* from, neighbor_t* end) {
+      for (; from < end; ++from) *from = neighbor_t{0, std::numeric_limits<float>::max()};
+    };
     rows_loop(nq, [&](uint64_t i) {
       neighbor_t* b = rows + i * k;
       if (e == 1.0f) {
         internal::knn_visitor<neighbor_t*> v(b, b + k);
         search_one(t, flat, view, q + i * t->dim, v);
+        fill(v.filled(), b + k);
       } else {
         internal::knn_visitor<neighbor_t*, true> v(b, b + k, e);
         search_one(t, flat, view, q + i * t->dim, v);
+        fill(v.filled(), b + k);
       }
     });
   } catch (const std::bad_alloc&) {
@@ -184,8 +191,10 @@ int ptk_host_search_knn_within(const ptk_tree* t, const float* points, const flo
       std::vector<neighbor_t> full(kk);
       internal::knn_visitor<neighbor_t*> v(full.data(), full.data() + kk);
       search_one(t, flat, view, q + i * t->dim, v);
+      // (only what the search wrote: a row no distance is below FLT_MAX from -- NaN, +-Inf -- accepts nothing)
+      const uint32_t found = (uint32_t)(v.filled() - full.data());
       uint32_t n = 0;
-      while (n < kk && full[n].distance < radius) {
+      while (n < found && full[n].distance < radius) {
         b[n] = full[n];
         ++n;
       }

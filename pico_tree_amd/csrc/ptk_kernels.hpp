@@ -168,15 +168,20 @@ __device__ __forceinline__ float sel3(uint32_t axis, float a0, float a1, float a
 // point distance that starts at 0 (internal::sum, metric.hpp:36-51; metric_lpinf: std::max from 0).
 // `init` is what a point distance starts from and `pad` the coordinate difference of an axis the
 // space does not have (dim < 3 in the 3-D kernels, the tail of a batch of coordinates elsewhere):
-// it must leave the distance as it is.
+// it must leave the distance as it is.  `first(diff)` is acc(init, diff), the first coordinate of a point distance: for
+// the two sums that is one(diff) (0 + x is x); for the max / min metrics it is NOT |diff| when diff is NaN -- std::max(0,
+// NaN) is 0 and std::min(FLT_MAX, NaN) is FLT_MAX (`a < b ? b : a`), so a NaN coordinate of a query is left out of
+// the distance whichever axis it is on (and std::min(FLT_MAX, +inf) is FLT_MAX).
 struct MetricL2 {  // metric_l2_squared
   static constexpr bool kMin = false;
   __device__ __forceinline__ static float one(float x) { return f_mul(x, x); }
+  __device__ __forceinline__ static float first(float diff) { return one(diff); }
   __device__ __forceinline__ static float acc(float d, float diff) { return f_add(d, f_mul(diff, diff)); }
 };
 struct MetricL1 {  // metric_l1
   static constexpr bool kMin = false;
   __device__ __forceinline__ static float one(float x) { return fabsf(x); }
+  __device__ __forceinline__ static float first(float diff) { return one(diff); }
   __device__ __forceinline__ static float acc(float d, float diff) { return f_add(d, fabsf(diff)); }
 };
 struct MetricLInf {  // metric_lpinf
@@ -186,6 +191,7 @@ struct MetricLInf {  // metric_lpinf
     const float a = fabsf(diff);
     return d < a ? a : d;  // std::max(d, a)
   }
+  __device__ __forceinline__ static float first(float diff) { return acc(0.0f, diff); }
 };
 // metric_lninf (metric.hpp:157-186): d = std::min(d, |x - y|) from the largest float, so the first
 // coordinate's |x - y| is `one`; an axis that does not exist must contribute +inf (kMin: the
@@ -197,6 +203,7 @@ struct MetricLNInf {
     const float a = fabsf(diff);
     return a < d ? a : d;  // std::min(d, a)
   }
+  __device__ __forceinline__ static float first(float diff) { return acc(3.402823466e+38f, diff); }
 };
 template <class M>
 __device__ __forceinline__ float metric_init() {  // what internal::sum / the min and max loops start from
@@ -209,7 +216,7 @@ __device__ __forceinline__ float metric_pad() {  // difference of a coordinate t
 // Three coordinates at once: acc(acc(acc(0, dx), dy), dz) without the exact no-op 0 + x.
 template <class M>
 __device__ __forceinline__ float point_distance3(float dx, float dy, float dz) {
-  return M::acc(M::acc(M::one(dx), dy), dz);
+  return M::acc(M::acc(M::first(dx), dy), dz);
 }
 
 // ---- record stack: ring of S slots in LDS + OVF spill slots in private scratch ----
@@ -376,11 +383,13 @@ struct KnnPolicy {  // search_visitor.hpp:83-123 / :198-247
     if constexpr (LIST_LDS) {
       for (uint32_t j = 0; j < filled; ++j) row[j] = get(j);
     }
-    if (filled < k) {  // fewer reachable points than k: the reference's sentinel (:102)
+    // Fewer accepted points than k: the reference writes its sentinel into slot k - 1 (:102) and leaves the slots
+    // between as it found them; here every such slot holds {0, FLT_MAX}, as the register lists leave them (ptk.h).
+    for (uint32_t j = filled; j < k; ++j) {
       Neighbor nb;
       nb.index = 0;
       nb.distance = 3.402823466e+38f;
-      row[k - 1] = nb;
+      row[j] = nb;
     }
   }
   __device__ __forceinline__ float max() const { return worst; }
@@ -868,7 +877,7 @@ __device__ __forceinline__ bool traverse(
             PTK_SCALAR(dx);
             PTK_SCALAR(dy);
             PTK_SCALAR(dz);
-            float dsum = M::one(dx);
+            float dsum = M::first(dx);
             PTK_SCALAR(dsum);
             dsum = M::acc(dsum, dy);
             PTK_SCALAR(dsum);
@@ -1148,11 +1157,13 @@ __global__ __launch_bounds__(BLOCK) void knn_kernel(
     Neighbor* row = out + qi * k;
     for (uint32_t j = 0; j < pol.filled; ++j) row[j] = pol.get(j);
   }
-  if (pol.filled < k) {  // k > reachable points: mirror the reference's sentinel (:102)
+  // Fewer accepted points than k (k > n_points, or a query row no distance is below FLT_MAX from): the reference's
+  // sentinel in slot k - 1 (:102), and {0, FLT_MAX} in every slot before it that the search did not write (ptk.h).
+  for (uint32_t j = pol.filled; j < k; ++j) {
     Neighbor nb;
     nb.index = 0;
     nb.distance = 3.402823466e+38f;
-    out[qi * k + (k - 1)] = nb;
+    out[qi * k + j] = nb;
   }
 }
 
@@ -2692,12 +2703,14 @@ __global__ __launch_bounds__(64) void box_kernel(
     const bool wrap = ((s1_mask >> axis) & 1u) != 0u && !(qn <= qx);
     return wrap ? (x >= qn || x <= qx) : (qn <= x && x <= qx);
   };
+  // box_base::contains (box.hpp:31-40) as it is written: outside iff `min > x || max < x`.  A NaN corner coordinate
+  // makes both comparisons false, so that side of the axis does not bound the box; `qn <= x && x <= qx` would reject.
+  auto in = [](float qn, float qx, float x) { return !(qn > x) && !(qx < x); };
   auto inside = [&]() {  // query_.contains(box_): both corners inside the closed query box
     if (TOPO)
       return seg_in(0, qn0, qx0, b.mn0, b.mx0) && seg_in(1, qn1, qx1, b.mn1, b.mx1) && seg_in(2, qn2, qx2, b.mn2, b.mx2);
-    return qn0 <= b.mn0 && b.mn0 <= qx0 && qn0 <= b.mx0 && b.mx0 <= qx0 &&
-           qn1 <= b.mn1 && b.mn1 <= qx1 && qn1 <= b.mx1 && b.mx1 <= qx1 &&
-           qn2 <= b.mn2 && b.mn2 <= qx2 && qn2 <= b.mx2 && b.mx2 <= qx2;
+    return in(qn0, qx0, b.mn0) && in(qn0, qx0, b.mx0) && in(qn1, qx1, b.mn1) && in(qn1, qx1, b.mx1) &&
+           in(qn2, qx2, b.mn2) && in(qn2, qx2, b.mx2);
   };
   auto report_range = [&](uint32_t begin, uint32_t end) {
     if (FILL) {
@@ -2722,7 +2735,7 @@ __global__ __launch_bounds__(64) void box_kernel(
       const float4 p = pts[begin + j];
       PTK_KEEP4(p);  // one 16-byte load: the index must not become a dependent load inside the branch
       const bool hit = TOPO ? (pt_in(0, qn0, qx0, p.x) && pt_in(1, qn1, qx1, p.y) && pt_in(2, qn2, qx2, p.z))
-                            : (qn0 <= p.x && p.x <= qx0 && qn1 <= p.y && p.y <= qx1 && qn2 <= p.z && p.z <= qx2);
+                            : (in(qn0, qx0, p.x) && in(qn1, qx1, p.y) && in(qn2, qx2, p.z));
       if (hit) {
         if (FILL) row[count] = __float_as_int(p.w);
         ++count;

@@ -247,7 +247,7 @@ __device__ __forceinline__ bool knn64_coop_sweep(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           if ((uint32_t)u < cnt) {
-            const double d = M::acc(M::acc(M::one(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u]));
+            const double d = M::acc(M::acc(M::first(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u]));
             if constexpr (COLLECT) {
               hit[u] = d <= fixed;
               hit_d[u] = d;
@@ -832,7 +832,7 @@ __global__ __launch_bounds__(64) void radius64_coop_count_kernel(
 #pragma unroll
           for (int u = 0; u < U; ++u) {
             if ((uint32_t)u < cnt) {
-              const double d = d_mul(M::acc(M::acc(M::one(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u])), e_inv);
+              const double d = d_mul(M::acc(M::acc(M::first(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u])), e_inv);
               l_mask |= (bound > d ? 1u : 0u) << l_pos;  // strict (:141)
               ++l_pos;
             }
@@ -993,7 +993,7 @@ __global__ __launch_bounds__(64) void radius64_coop_replay_kernel(
         Neighbor64 nb;
         nb.index = (int32_t)__double_as_longlong(a.w);
         nb.pad_ = 0;
-        nb.distance = d_mul(M::acc(M::acc(M::one(d_sub(q0, a.x)), d_sub(q1, a.y)), d_sub(q2, a.z)), e_inv);
+        nb.distance = d_mul(M::acc(M::acc(M::first(d_sub(q0, a.x)), d_sub(q1, a.y)), d_sub(q2, a.z)), e_inv);
         out[w++] = nb;
       }
       at += (uint32_t)__shfl((int)incl, 63);

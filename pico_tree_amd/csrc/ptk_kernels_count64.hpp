@@ -215,7 +215,7 @@ __global__ __launch_bounds__(64) void count64_within_kernel(
 #pragma unroll
         for (int u = 0; u < kLeaf64; ++u) {
           if (j + u < n) {
-            const double d = M::acc(M::acc(M::one(d_sub(qx, px[u])), d_sub(qy, py[u])), d_sub(qz, pz[u]));
+            const double d = M::acc(M::acc(M::first(d_sub(qx, px[u])), d_sub(qy, py[u])), d_sub(qz, pz[u]));
             count += radius > d ? 1u : 0u;  // strict
           }
         }

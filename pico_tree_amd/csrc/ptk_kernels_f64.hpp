@@ -76,12 +76,14 @@ struct Metric64L2 {
   static constexpr bool kMin = false;
   static constexpr bool kTopo = false;
   __device__ __forceinline__ static double one(double x) { return d_mul(x, x); }
+  __device__ __forceinline__ static double first(double diff) { return one(diff); }  // (acc(init, diff): see MetricL2)
   __device__ __forceinline__ static double acc(double d, double diff) { return d_add(d, d_mul(diff, diff)); }
 };
 struct Metric64L1 {
   static constexpr bool kMin = false;
   static constexpr bool kTopo = false;
   __device__ __forceinline__ static double one(double x) { return fabs(x); }
+  __device__ __forceinline__ static double first(double diff) { return one(diff); }
   __device__ __forceinline__ static double acc(double d, double diff) { return d_add(d, fabs(diff)); }
 };
 struct Metric64LInf {
@@ -92,6 +94,7 @@ struct Metric64LInf {
     const double a = fabs(diff);
     return d < a ? a : d;  // std::max(d, a)
   }
+  __device__ __forceinline__ static double first(double diff) { return acc(0.0, diff); }
 };
 struct Metric64LNInf {  // metric_lninf, as MetricLNInf of ptk_kernels.hpp
   static constexpr bool kMin = true;
@@ -101,6 +104,7 @@ struct Metric64LNInf {  // metric_lninf, as MetricLNInf of ptk_kernels.hpp
     const double a = fabs(diff);
     return a < d ? a : d;  // std::min(d, a)
   }
+  __device__ __forceinline__ static double first(double diff) { return acc(1.7976931348623157e+308, diff); }
 };
 template <class M>
 __device__ __forceinline__ double metric64_init() {
@@ -254,12 +258,14 @@ struct Knn64Policy {  // :83-123 / :198-247
     }
   }
   __device__ __forceinline__ void end_query() {
-    if (filled < k) {  // fewer reachable points than k: the reference's sentinel (:102)
+    // Fewer accepted points than k: the reference's sentinel in slot k - 1 (:102), and the same {0, DBL_MAX} in every
+    // slot before it that the search did not write, as the register lists leave them (ptk.h).
+    for (uint32_t j = filled; j < k; ++j) {
       Neighbor64 nb;
       nb.index = 0;
       nb.pad_ = 0;
       nb.distance = kDblMax;
-      list[k - 1] = nb;
+      list[j] = nb;
     }
   }
 };
@@ -591,7 +597,7 @@ __device__ __forceinline__ bool traverse64_3(const DevTree64& t, double q0, doub
         for (int u = 0; u < kLeaf64; ++u) {
           if (j + u < count) {
             // internal::sum (metric.hpp:36-51) from d = 0: acc(0, x) == one(x) exactly
-            pol.visit(pi[u], M::acc(M::acc(M::one(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u])));
+            pol.visit(pi[u], M::acc(M::acc(M::first(d_sub(q0, px[u])), d_sub(q1, py[u])), d_sub(q2, pz[u])));
           }
         }
       }
@@ -966,7 +972,7 @@ __global__ __launch_bounds__(64) void box64_kernel(
         const bool wrap = ((s1_mask >> a) & 1u) != 0u && !(lo <= hi);
         in = in && (wrap ? (bl >= lo || bh <= hi) : (lo <= bl && bh <= hi));
       } else {
-        in = in && lo <= bl && bl <= hi && lo <= bh && bh <= hi;
+        in = in && !(lo > bl) && !(hi < bl) && !(lo > bh) && !(hi < bh);  // box_base::contains as written: NaN does not bound
       }
     }
     return in;
@@ -996,7 +1002,7 @@ __global__ __launch_bounds__(64) void box64_kernel(
       for (uint32_t a = 0; a < dim; ++a) {
         const double lo = qn[a * 64], hi = qx[a * 64];
         const bool wrap = TOPO && ((s1_mask >> a) & 1u) != 0u && !(lo <= hi);
-        in = in && (wrap ? (p[a] >= lo || p[a] <= hi) : (lo <= p[a] && p[a] <= hi));
+        in = in && (wrap ? (p[a] >= lo || p[a] <= hi) : TOPO ? (lo <= p[a] && p[a] <= hi) : (!(lo > p[a]) && !(hi < p[a])));
       }
       if (in) {
         if (FILL) row[count] = t.index[begin + j];

@@ -339,11 +339,13 @@ __global__ __launch_bounds__(64) void box_nd_kernel(
 
   PTK_STACK(S, OVF, 64, st, t);
 
+  // (box_base::contains as it is written, box.hpp:31-40: outside iff `min > x || max < x` -- a NaN corner coordinate
+  // does not bound its side of the axis)
   auto inside = [&]() {  // query_.contains(box_), box.hpp: both corners inside the closed query box
     bool in = true;
     for (uint32_t a = 0; a < dim; ++a) {
       const float lo = qn[a * 64], hi = qx[a * 64], bl = mn[a * 64], bh = mx[a * 64];
-      in = in && lo <= bl && bl <= hi && lo <= bh && bh <= hi;
+      in = in && !(lo > bl) && !(hi < bl) && !(lo > bh) && !(hi < bh);
     }
     return in;
   };
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(64) void box_nd_kernel(
     for (uint32_t j = 0; j < n; ++j) {
       const float* p = t.pts + (uint64_t)(begin + j) * dim;
       bool in = true;
-      for (uint32_t a = 0; a < dim; ++a) in = in && qn[a * 64] <= p[a] && p[a] <= qx[a * 64];
+      for (uint32_t a = 0; a < dim; ++a) in = in && !(qn[a * 64] > p[a]) && !(qx[a * 64] < p[a]);
       if (in) {
         if (FILL) row[count] = t.index[begin + j];
         ++count;

@@ -597,14 +597,18 @@ def test_gpu_double_capped_radius_and_its_cooperative_count(gpu, case):
 @pytest.mark.gpu
 def test_gpu_double_k_larger_than_the_tree(gpu):
     """k > n_points on a float64 tree: as the float32 entry (tests/test_gpu_parity.py::test_k_larger_than_the_tree):
-    the n neighbours in order, the DBL_MAX sentinel in the last slot (search_visitor.hpp:95-110)."""
+    the n neighbours in order, the DBL_MAX sentinel in the last slot (search_visitor.hpp:95-110), {0, DBL_MAX} in the
+    slots between (ptk.h: every slot no search wrote), padding zero -- whatever the buffer held."""
     rng = np.random.default_rng(44)
     pts, q = rng.random((7, 3)), rng.random((50, 3))
     t = pt.KdTree(pts, pt.Metric.L2Squared, 3, device=gpu)
     ref = oracle.Oracle(pts, 3, "port", dtype=np.float64)
-    got, want = t.search_knn(q, 12), ref.search_knn(q, 7)
+    nns = np.empty((50, 12), dtype=pt.NEIGHBOR64)
+    nns.view(np.uint8).reshape(-1)[:] = 0xA5
+    got, want = t.search_knn(q, 12, nns), ref.search_knn(q, 7)
     assert got.shape == (50, 12) and same(got[:, :7], want["index"], want["distance"])
-    assert np.all(got["distance"][:, 11] == np.finfo(np.float64).max)
+    assert np.all(got["distance"][:, 7:] == np.finfo(np.float64).max) and np.all(got["index"][:, 7:] == 0)
+    assert not got.view(np.uint8).reshape(50, 12, 16)[:, :, 4:8].any()
 
 
 @pytest.mark.gpu

@@ -403,15 +403,18 @@ def test_tree_deeper_than_the_private_stack_classes(gpu, monkeypatch):
 
 def test_k_larger_than_the_tree(gpu):
     """k > n_points: the reference's iterator-range search_knn (and its Python binding) fills the n
-    neighbours and leaves the FLT_MAX sentinel in the last slot (search_visitor.hpp:95-110)."""
+    neighbours and leaves the FLT_MAX sentinel in the last slot (search_visitor.hpp:95-110); the slots in between, the
+    caller's in the reference, hold {0, FLT_MAX} as every slot no search wrote (ptk.h) -- whatever the buffer held."""
     pts, q = ds.uniform_cloud(7, 3, 41), ds.uniform_cloud(50, 3, 42)
     tree = pt.KdTree(pts, pt.Metric.L2Squared, 3, device=gpu)
     ref = oracle.Oracle(pts, 3, "port")
-    got = tree.search_knn(q, 12)
+    nns = np.empty((50, 12), dtype=pt.NEIGHBOR)
+    nns.view(np.uint8).reshape(-1)[:] = 0xA5
+    got = tree.search_knn(q, 12, nns)
     want = ref.search_knn(q, 7)
     assert got.shape == (50, 12)
     assert got[:, :7].tobytes() == want.tobytes()
-    assert np.all(got["distance"][:, 11] == np.float32(3.402823466e+38))
+    assert np.all(got["distance"][:, 7:] == np.float32(3.402823466e+38)) and np.all(got["index"][:, 7:] == 0)
 
 
 def test_host_radius_passes_do_not_reuse_a_stale_capture(trees):
