@@ -578,6 +578,19 @@ int make_permutation(const ptk_tree* t, const float* d_q, uint64_t nq, hipStream
   return PTK_OK;
 }
 
+// The launch order of a batch, as every search that takes one asks for it: reserves `extra_bytes` of the caller's own
+// plus, where the handle's reorder mode wants the batch sorted (want_reorder), the arrays of the sort, then sorts
+// (make_permutation: `heavy_first` and `may_skip` are its).  *perm: the rows in launch order (Morton order along the
+// first three axes, whatever the dimension), or nullptr for a batch that is launched as it came.
+int order_batch(const ptk_tree* t, const float* d_q, uint64_t nq, hipStream_t s, Scratch& scratch, size_t extra_bytes,
+                uint32_t** perm, uint32_t heavy_first = 0, bool may_skip = false) {
+  *perm = nullptr;
+  const bool reorder = want_reorder(t, nq);
+  const int rc = scratch.reserve(extra_bytes + (reorder ? permutation_scratch_bytes(nq) : 0));
+  if (rc != PTK_OK || !reorder) return rc;
+  return make_permutation(t, d_q, nq, s, scratch, perm, heavy_first, may_skip);
+}
+
 // PTK_RADIUS_CAPTURE_MB: the most device memory the captured rows of a radius batch may take
 // (default 16384; 0 switches the capture off and every fill pass repeats the traversal).
 size_t capture_budget_bytes(const ptk_tree* t) {
@@ -950,6 +963,66 @@ int dispatch_knn1(const ptk_tree* t, const float* d_q, const uint32_t* perm, uin
   return dispatch_knn1_of<ptk::MetricL2>(t, d_q, perm, nq, e, d_out, s, scratch);
 }
 
+// A deep tree (deep_tree(t): deeper than the private stack classes, any k, any metric) is searched a few queries at a
+// time, the record stacks spilling to HBM.  The spill block comes out of `scratch` -- reserved here (deep_plan) unless
+// the caller has reserved it with bytes of its own --, then `launch(dev, lo, n)` runs per piece of the plan, `dev` being
+// the handle's tree view with the spill bound to it: ptk::DevTree for dim <= 3, ptk::DevTreeND above.  One profile
+// section around all pieces (Timer::stop(kind, queries)); the launch error is looked at after every piece.
+template <class Launch>
+int deep_pieces(const ptk_tree* t, uint64_t nq, hipStream_t s, Scratch& scratch, int kind, uint64_t queries, Launch&& launch) {
+  const DeepPlan plan = deep_plan(t, nq);
+  if (!scratch.reserved()) {
+    const int rc = scratch.reserve(plan.bytes());
+    if (rc != PTK_OK) return rc;
+  }
+  ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
+  if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
+  ptk::DevTree dev = t->dev;
+  dev.deep_spill = spill;
+  dev.deep_cap = plan.cap;
+  ptk::DevTreeND dev_nd = t->dev_nd;
+  dev_nd.deep_spill = spill;
+  dev_nd.deep_cap = plan.cap;
+  Timer timer(t, s);
+  for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
+    const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
+    const int rc = t->dim > 3 ? launch(dev_nd, lo, n) : launch(dev, lo, n);
+    if (rc != PTK_OK) return rc;
+    PTK_HIP(hipGetLastError());
+  }
+  timer.stop(kind, queries);
+  return PTK_OK;
+}
+// (the deep launches of ptk_family_nd.hip under the names of their 3-D forms: deep_pieces hands its callable either view)
+int knn_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float e,
+             ptk::Neighbor* d_out, hipStream_t s) {
+  return ptkf::knn_nd_deep(t, dev, d_q, n, k, e, d_out, s);
+}
+int knn_within_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
+                    ptk::Neighbor* d_out, hipStream_t s) {
+  return ptkf::knn_nd_within_deep(t, dev, d_q, n, k, radius, d_out, s);
+}
+int radius_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, float radius, float e, bool fill,
+                uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
+  return ptkf::radius_nd_deep(t, dev, d_q, n, radius, e, fill, d_counts, d_offsets, d_out, s);
+}
+using ptkf::knn_deep;
+using ptkf::knn_within_deep;
+using ptkf::radius_deep;
+
+// Very large batches go through in pieces of at most 2^25 queries: the scratch of a piece stays
+// at a few GB and every 32-bit index in the kernels holds (PTK_MAX_BATCH shrinks it for tests).
+// `search(first, n)` takes rows [first, first + n) of the batch.
+template <class Search>
+int in_batch_pieces(uint64_t nq, Search&& search) {
+  const uint64_t piece = (uint64_t)std::max(1, env_int("PTK_MAX_BATCH", 1 << 25));
+  for (uint64_t done = 0; done < nq; done += piece) {
+    const int rc = search(done, std::min(piece, nq - done));
+    if (rc != PTK_OK) return rc;
+  }
+  return PTK_OK;
+}
+
 }  // namespace
 
 namespace ptkf {
@@ -1307,32 +1380,15 @@ int ptk_tree_set_reorder(ptk_tree* t, int mode) {
 
 // ---- knn --------------------------------------------------------------------------------
 
-int ptk_search_knn_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float e,
-                          ptk_neighbor* d_out, void* stream) {
-  int rc = check_search(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(e > 0.0f)) return fail(PTK_ERR_INVALID, "approximation ratio e must be > 0");
-  if (nq == 0) return PTK_OK;
-  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  hipStream_t s = static_cast<hipStream_t>(stream);
+// One piece of a k-NN batch (at most PTK_MAX_BATCH queries), the arguments checked.
+static int knn_piece_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float e, ptk::Neighbor* d_out,
+                            hipStream_t s) {
   // k > n_points: what the reference's iterator-range search_knn does with a range longer than the
   // tree (search_visitor.hpp:95-110; its Python binding passes k through unclamped): the n_points
   // neighbours in order, the last slot's distance left at the FLT_MAX sentinel.  The slots in
   // between are the caller's in the reference; here they hold {0, FLT_MAX} as every slot a search did
   // not write (ptk.h; KnnPolicy::end_query).  (These rows take the list-in-the-row kernels.)
   const bool short_tree = k > t->n_points;
-  // Very large batches go through in pieces of at most 2^25 queries: the scratch of a piece stays
-  // at a few GB and every 32-bit index in the kernels holds (PTK_MAX_BATCH shrinks it for tests).
-  const uint64_t piece = (uint64_t)std::max(1, env_int("PTK_MAX_BATCH", 1 << 25));
-  if (nq > piece) {
-    for (uint64_t done = 0; done < nq; done += piece) {
-      const uint64_t n = std::min(piece, nq - done);
-      rc = ptk_search_knn_device(t, d_q + done * t->dim, n, k, e, d_out + done * k, stream);
-      if (rc != PTK_OK) return rc;
-    }
-    return PTK_OK;
-  }
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   const bool l2 = t->metric.load() == PTK_METRIC_L2_SQUARED;
@@ -1343,74 +1399,49 @@ int ptk_search_knn_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint
   const bool two_phase = k == 1 && t->dim <= 3 && (l2 || (t->metric.load() == PTK_METRIC_L1 && t->n_piles == 0));
   if (topological(t)) {
     if (deep_tree(t)) return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
-    const bool reorder = want_reorder(t, nq);
     Scratch scratch(t, s, /*per_stream=*/true);
-    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
-    if (rc != PTK_OK) return rc;
     uint32_t* perm = nullptr;
-    if (reorder) {
-      rc = make_permutation(t, d_q, nq, s, scratch, &perm);
-      if (rc != PTK_OK) return rc;
-    }
-    return ptkf::knn_topo(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor*>(d_out), s, short_tree);
+    const int rc = order_batch(t, d_q, nq, s, scratch, 0, &perm);
+    if (rc != PTK_OK) return rc;
+    return ptkf::knn_topo(t, d_q, perm, nq, k, e, d_out, s, short_tree);
   }
   const bool knn1_view = k == 1 && l2 && t->dim <= 3 && t->n_piles != 0 && ovf_class_of(knn1_depth(t), 16) != kDeepClass;
   if (deep_tree(t) && !knn1_view) {  // a few queries at a time, the record stacks spilling to HBM (any k, any metric)
-    const DeepPlan plan = deep_plan(t, nq);
     Scratch scratch(t, s, /*per_stream=*/true);
-    rc = scratch.reserve(plan.bytes());
-    if (rc != PTK_OK) return rc;
-    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
-    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
-    auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
-    Timer timer(t, s);
-    for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
-      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
-      if (t->dim > 3) {
-        ptk::DevTreeND dev = t->dev_nd;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::knn_nd_deep(t, dev, d_q + lo * t->dim, n, k, e, o + lo * k, s);
-      } else {
-        ptk::DevTree dev = t->dev;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::knn_deep(t, dev, d_q + lo * t->dim, n, k, e, o + lo * k, s);
-      }
-      if (rc != PTK_OK) return rc;
-      PTK_HIP(hipGetLastError());
-    }
-    timer.stop(0, nq);
-    return PTK_OK;
+    return deep_pieces(t, nq, s, scratch, 0, nq, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return knn_deep(t, dev, d_q + lo * t->dim, n, k, e, d_out + lo * k, s);
+    });
   }
-  const bool reorder = want_reorder(t, nq);
   Scratch scratch(t, s, /*per_stream=*/true);
-  rc = scratch.reserve((reorder ? permutation_scratch_bytes(nq) : 0) +
-                       (two_phase ? two_phase_scratch_bytes(t, nq) : 0) +
-                       (k > 1 && k <= 64 && (l2 || t->metric.load() == PTK_METRIC_L1) && t->dim <= 3 && knn_cap(e, nq, k) != 0u
-                            ? knn_coop_scratch_bytes(t, nq)
-                            : 0));
-  if (rc != PTK_OK) return rc;
+  // (the general kernels run every query to its end in its lane: the expensive queries to the front of the launch)
+  // (the two-phase k = 1 search orders its own continuations: a batch that arrives coherent is not sorted again --
+  // REORDER_AUTO only; the general kernels want the expensive queries in front whatever the order)
+  const bool may_skip = two_phase && t->reorder.load() == PTK_REORDER_AUTO;
   uint32_t* perm = nullptr;
-  if (reorder) {  // Morton order along the first three axes, whatever the dimension
-    // (the general kernels run every query to its end in its lane: the expensive queries to the front of the launch)
-    // (the two-phase k = 1 search orders its own continuations: a batch that arrives coherent is not sorted again --
-    // REORDER_AUTO only; the general kernels want the expensive queries in front whatever the order)
-    const bool may_skip = two_phase && t->reorder.load() == PTK_REORDER_AUTO;
-    rc = make_permutation(t, d_q, nq, s, scratch, &perm, t->dim <= 3 && !two_phase ? ptk::kCellsEmptyFirst : 0u, may_skip);
-    if (rc != PTK_OK) return rc;
-  }
-  if (t->dim > 3) {
-    return ptkf::knn_nd(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor*>(d_out), s, short_tree);
-  }
-  if (two_phase) {
-    rc = dispatch_knn1(t, d_q, perm, nq, e, reinterpret_cast<ptk::Neighbor*>(d_out), s, scratch);
-  } else if (k <= knn_reg_max(l2) && !short_tree) {
-    rc = ptkf::knn_reg(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor*>(d_out), s, &scratch);
-  } else {
-    rc = ptkf::knn_rows(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor*>(d_out), s);
-  }
-  return rc;
+  const int rc = order_batch(t, d_q, nq, s, scratch,
+                         (two_phase ? two_phase_scratch_bytes(t, nq) : 0) +
+                             (k > 1 && k <= 64 && (l2 || t->metric.load() == PTK_METRIC_L1) && t->dim <= 3 && knn_cap(e, nq, k) != 0u
+                                  ? knn_coop_scratch_bytes(t, nq)
+                                  : 0),
+                         &perm, t->dim <= 3 && !two_phase ? ptk::kCellsEmptyFirst : 0u, may_skip);
+  if (rc != PTK_OK) return rc;
+  if (t->dim > 3) return ptkf::knn_nd(t, d_q, perm, nq, k, e, d_out, s, short_tree);
+  if (two_phase) return dispatch_knn1(t, d_q, perm, nq, e, d_out, s, scratch);
+  if (k <= knn_reg_max(l2) && !short_tree) return ptkf::knn_reg(t, d_q, perm, nq, k, e, d_out, s, &scratch);
+  return ptkf::knn_rows(t, d_q, perm, nq, k, e, d_out, s);
+}
+
+int ptk_search_knn_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float e,
+                          ptk_neighbor* d_out, void* stream) {
+  int rc = check_search(t, d_q, nq);
+  if (rc == PTK_OK) rc = check_k(k);
+  if (rc == PTK_OK) rc = check_ratio(e);
+  if (rc != PTK_OK || nq == 0) return rc;
+  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  return in_batch_pieces(nq, [&](uint64_t first, uint64_t n) {
+    return knn_piece_device(t, d_q + first * t->dim, n, k, e, reinterpret_cast<ptk::Neighbor*>(d_out) + first * k,
+                            static_cast<hipStream_t>(stream));
+  });
 }
 
 // Grow-only device block of the host-buffer entry points (rounded up to 1 MiB; the old contents are dropped).
@@ -1761,97 +1792,74 @@ static float within_seed(const ptk_tree* t, float radius) {
   return std::isfinite(seed) ? seed : 3.402823466e+38f;
 }
 
-int ptk_search_knn_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float radius,
-                                 ptk_neighbor* d_out, void* stream) {
-  int rc = check_search(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // (pieces of at most PTK_MAX_BATCH queries, as ptk_search_knn_device)
-  const uint64_t piece = (uint64_t)std::max(1, env_int("PTK_MAX_BATCH", 1 << 25));
-  if (nq > piece) {
-    for (uint64_t done = 0; done < nq; done += piece) {
-      const uint64_t n = std::min(piece, nq - done);
-      rc = ptk_search_knn_within_device(t, d_q + done * t->dim, n, k, radius, d_out + done * k, stream);
-      if (rc != PTK_OK) return rc;
-    }
-    return PTK_OK;
-  }
+// One piece of a bounded k-NN batch (at most PTK_MAX_BATCH queries, as knn_piece_device), the arguments checked.
+static int knn_within_piece_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float radius,
+                                   ptk::Neighbor* d_out, hipStream_t s) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
+  Scratch scratch(t, s, /*per_stream=*/true);
   if (deep_tree(t)) {  // the deep stack class: the margin assumes shallower trees -- unseeded, masked at store
-    const DeepPlan plan = deep_plan(t, nq);
-    Scratch scratch(t, s, /*per_stream=*/true);
-    rc = scratch.reserve(plan.bytes());
-    if (rc != PTK_OK) return rc;
-    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
-    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
-    Timer timer(t, s);
-    for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
-      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
-      if (t->dim > 3) {
-        ptk::DevTreeND dev = t->dev_nd;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::knn_nd_within_deep(t, dev, d_q + lo * t->dim, n, k, radius, o + lo * k, s);
-      } else {
-        ptk::DevTree dev = t->dev;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::knn_within_deep(t, dev, d_q + lo * t->dim, n, k, radius, o + lo * k, s);
-      }
-      if (rc != PTK_OK) return rc;
-    }
-    timer.stop(0, nq);
-    return PTK_OK;
+    return deep_pieces(t, nq, s, scratch, 0, nq, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return knn_within_deep(t, dev, d_q + lo * t->dim, n, k, radius, d_out + lo * k, s);
+    });
   }
   const float seed = within_seed(t, radius);
-  const bool reorder = want_reorder(t, nq);
-  Scratch scratch(t, s, /*per_stream=*/true);
-  rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
-  if (rc != PTK_OK) return rc;
+  // (as the general k-NN kernels: the expensive queries to the front of the launch)
   uint32_t* perm = nullptr;
-  if (reorder) {  // (as the general k-NN kernels: the expensive queries to the front of the launch)
-    rc = make_permutation(t, d_q, nq, s, scratch, &perm, t->dim <= 3 ? ptk::kCellsEmptyFirst : 0u);
-    if (rc != PTK_OK) return rc;
-  }
-  if (t->dim > 3) return ptkf::knn_nd_within(t, d_q, perm, nq, k, seed, radius, o, s);
-  return ptkf::knn_within(t, d_q, perm, nq, k, seed, radius, o, s);
+  const int rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, t->dim <= 3 ? ptk::kCellsEmptyFirst : 0u);
+  if (rc != PTK_OK) return rc;
+  if (t->dim > 3) return ptkf::knn_nd_within(t, d_q, perm, nq, k, seed, radius, d_out, s);
+  return ptkf::knn_within(t, d_q, perm, nq, k, seed, radius, d_out, s);
 }
 
-// Host buffers: the batch goes up, is searched on one stream of the handle and comes down, under the handle's I/O lock.
-int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32_t k, float radius, ptk_neighbor* out) {
-  int rc = check_search(t, q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+int ptk_search_knn_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, float radius,
+                                 ptk_neighbor* d_out, void* stream) {
+  const int rc = check_knn_within(t, d_q, nq, k, radius, d_out);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return in_batch_pieces(nq, [&](uint64_t first, uint64_t n) {
+    return knn_within_piece_device(t, d_q + first * t->dim, n, k, radius,
+                                   reinterpret_cast<ptk::Neighbor*>(d_out) + first * k, static_cast<hipStream_t>(stream));
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The host-buffer form of a search whose rows have one size: the batch goes up, is searched on one stream of the
+// handle and comes down, under the handle's I/O lock.  `search(d_q, d_out, stream)` is the _device form.
+template <class Search>
+int host_round_trip(const ptk_tree* t, const float* q, uint64_t nq, void* out, size_t out_bytes, Search&& search) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t row_in = (size_t)t->dim * sizeof(float), row_out = (size_t)k * sizeof(ptk_neighbor);
+  const size_t in_bytes = (size_t)nq * t->dim * sizeof(float);
   HostIo& io = t->io;
   std::lock_guard<std::mutex> lock(io.mutex);
   if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  rc = grow_device_block(&io.d_in, &io.in_capacity, (size_t)nq * row_in);
-  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, (size_t)nq * row_out);
+  int rc = grow_device_block(&io.d_in, &io.in_capacity, in_bytes);
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
   if (rc != PTK_OK) return rc;
-  PTK_HIP(hipMemcpyAsync(io.d_in, q, (size_t)nq * row_in, hipMemcpyHostToDevice, io.search[0]));
-  rc = ptk_search_knn_within_device(t, reinterpret_cast<const float*>(io.d_in), nq, k, radius,
-                                    reinterpret_cast<ptk_neighbor*>(io.d_out), io.search[0]);
+  PTK_HIP(hipMemcpyAsync(io.d_in, q, in_bytes, hipMemcpyHostToDevice, io.search[0]));
+  rc = search(reinterpret_cast<const float*>(io.d_in), io.d_out, io.search[0]);
   if (rc != PTK_OK) {
     (void)hipStreamSynchronize(io.search[0]);
     return rc;
   }
-  PTK_HIP(hipMemcpyAsync(out, io.d_out, (size_t)nq * row_out, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipMemcpyAsync(out, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
   PTK_HIP(hipStreamSynchronize(io.search[0]));
   return PTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32_t k, float radius, ptk_neighbor* out) {
+  const int rc = check_knn_within(t, q, nq, k, radius, out);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return host_round_trip(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor), [&](const float* d_q, char* d_out, hipStream_t s) {
+    return ptk_search_knn_within_device(t, d_q, nq, k, radius, reinterpret_cast<ptk_neighbor*>(d_out), s);
+  });
 }
 
 // ---- neighbour counts within a radius ---------------------------------------
@@ -1876,11 +1884,8 @@ static int count_table_of(const ptk_tree* t, hipStream_t s) {
 // dim > 3, the topological metrics and deep trees the count kernels of the radius search, clamped afterwards.
 int ptk_search_count_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, uint64_t max_count,
                                    uint64_t* d_counts, void* stream) {
-  int rc = check_search(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (d_counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  int rc = check_count_within(t, d_q, nq, radius, d_counts);
+  if (rc != PTK_OK || nq == 0) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
@@ -1889,48 +1894,21 @@ int ptk_search_count_within_device(const ptk_tree* t, const float* d_q, uint64_t
     rc = count_table_of(t, s);
     if (rc != PTK_OK) return rc;
   }
-  const bool reorder = want_reorder(t, nq);
   Scratch scratch(t, s, /*per_stream=*/true);
+  uint32_t* perm = nullptr;
   if (topological(t)) {
     if (deep_tree(t)) return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
-    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+    rc = order_batch(t, d_q, nq, s, scratch, 0, &perm);
     if (rc != PTK_OK) return rc;
-    uint32_t* perm = nullptr;
-    if (reorder) {
-      rc = make_permutation(t, d_q, nq, s, scratch, &perm);
-      if (rc != PTK_OK) return rc;
-    }
     rc = ptkf::radius_topo(t, d_q, perm, nq, radius, 1.0f, false, d_counts, nullptr, nullptr, s);
   } else if (deep_tree(t)) {  // record stacks spilling to HBM, a few queries per launch
-    const DeepPlan plan = deep_plan(t, nq);
-    rc = scratch.reserve(plan.bytes());
-    if (rc != PTK_OK) return rc;
-    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
-    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
-    Timer timer(t, s);
-    for (uint64_t lo = 0; lo < nq && rc == PTK_OK; lo += plan.piece) {
-      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
-      if (nd) {
-        ptk::DevTreeND dev = t->dev_nd;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::radius_nd_deep(t, dev, d_q + lo * t->dim, n, radius, 1.0f, false, d_counts + lo, nullptr, nullptr, s);
-      } else {
-        ptk::DevTree dev = t->dev;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::radius_deep(t, dev, d_q + lo * t->dim, n, radius, 1.0f, false, d_counts + lo, nullptr, nullptr, s);
-      }
-    }
-    timer.stop(0, nq);
+    rc = deep_pieces(t, nq, s, scratch, 0, nq, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return radius_deep(t, dev, d_q + lo * t->dim, n, radius, 1.0f, false, d_counts + lo, nullptr, nullptr, s);
+    });
   } else {
-    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+    // (the batch order of the radius count pass: a query costs what it finds, the densest cells first)
+    rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, nd ? 0u : ptk::kCellsDenseFirst);
     if (rc != PTK_OK) return rc;
-    uint32_t* perm = nullptr;
-    if (reorder) {  // (the batch order of the radius count pass: a query costs what it finds, the densest cells first)
-      rc = make_permutation(t, d_q, nq, s, scratch, &perm, nd ? 0u : ptk::kCellsDenseFirst);
-      if (rc != PTK_OK) return rc;
-    }
     if (!nd)
       return ptkf::count_within(t, d_q, perm, nq, radius, max_count, knob_int("count_shortcut", 1) != 0, d_counts, s);
     rc = ptkf::radius_nd(t, d_q, nq, radius, 1.0f, false, d_counts, nullptr, nullptr, s, perm);
@@ -1939,33 +1917,13 @@ int ptk_search_count_within_device(const ptk_tree* t, const float* d_q, uint64_t
   return ptkf::clamp_counts(d_counts, nq, max_count, s);
 }
 
-// Host buffers: the batch goes up, is counted on one stream of the handle and comes down, under the handle's I/O lock.
 int ptk_search_count_within(const ptk_tree* t, const float* q, uint64_t nq, float radius, uint64_t max_count,
                             uint64_t* counts) {
-  int rc = check_search(t, q, nq);
-  if (rc != PTK_OK) return rc;
-  if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t row_in = (size_t)t->dim * sizeof(float);
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  rc = grow_device_block(&io.d_in, &io.in_capacity, (size_t)nq * row_in);
-  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, (size_t)nq * sizeof(uint64_t));
-  if (rc != PTK_OK) return rc;
-  PTK_HIP(hipMemcpyAsync(io.d_in, q, (size_t)nq * row_in, hipMemcpyHostToDevice, io.search[0]));
-  rc = ptk_search_count_within_device(t, reinterpret_cast<const float*>(io.d_in), nq, radius, max_count,
-                                      reinterpret_cast<uint64_t*>(io.d_out), io.search[0]);
-  if (rc != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
-    return rc;
-  }
-  PTK_HIP(hipMemcpyAsync(counts, io.d_out, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
-  return PTK_OK;
+  const int rc = check_count_within(t, q, nq, radius, counts);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return host_round_trip(t, q, nq, counts, (size_t)nq * sizeof(uint64_t), [&](const float* d_q, char* d_out, hipStream_t s) {
+    return ptk_search_count_within_device(t, d_q, nq, radius, max_count, reinterpret_cast<uint64_t*>(d_out), s);
+  });
 }
 
 // ---- radius -------------------------------------------------------------------------------
@@ -1974,14 +1932,14 @@ static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, 
                               uint64_t* d_counts, const uint64_t* d_offsets, ptk_neighbor* d_out, int sort,
                               hipStream_t s) {
   int rc = check_search(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (!(e > 0.0f)) return fail(PTK_ERR_INVALID, "approximation ratio e must be > 0");
-  if (nq == 0) return PTK_OK;
+  if (rc == PTK_OK) rc = check_ratio(e);
+  if (rc != PTK_OK || nq == 0) return rc;
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   const bool nd = t->dim > 3;
-  const bool reorder = want_reorder(t, nq);  // Morton order along the first three axes, whatever the dimension
   const int metric = t->metric.load();
+  auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
+  uint32_t* perm = nullptr;
   Scratch scratch(t, s);
   Workspace& ws = t->ws;  // locked by `scratch` for the duration of this call
   // A fill pass that repeats the arguments of the last count pass is served from its capture.
@@ -1996,73 +1954,41 @@ static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, 
     uint32_t* n_over = scratch.take<uint32_t>(1);
     if (over_list == nullptr || n_over == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
     if (ws.cap_lists) {  // (3-D trees: the rows are made from the leaf lists of the count pass)
-      rc = ptkf::radius_replay(t, d_q, e, ws.cap, d_offsets, reinterpret_cast<ptk::Neighbor*>(d_out), over_list, n_over, s,
+      rc = ptkf::radius_replay(t, d_q, e, ws.cap, d_offsets, o, over_list, n_over, s,
                                ws.cap_heavy.max_heavy != 0u ? &ws.cap_heavy : nullptr);
       if (rc != PTK_OK) return rc;
     } else {
-      rc = ptkf::radius_log_scatter(t, ws.cap, d_offsets, reinterpret_cast<ptk::Neighbor*>(d_out), over_list, n_over, s);
+      rc = ptkf::radius_log_scatter(t, ws.cap, d_offsets, o, over_list, n_over, s);
       if (rc != PTK_OK) return rc;
     }
     // Rows the capture could not hold (possibly none: the blocks then leave at once).
     if (nd) {
-      rc = ptkf::radius_nd(t, d_q, nq, radius, e, true, nullptr, d_offsets, reinterpret_cast<ptk::Neighbor*>(d_out), s,
-                           over_list, n_over);
+      rc = ptkf::radius_nd(t, d_q, nq, radius, e, true, nullptr, d_offsets, o, s, over_list, n_over);
     } else {
-      rc = ptkf::radius_traverse(t, d_q, over_list, n_over_max, radius, e, true, nullptr, d_offsets,
-                                 reinterpret_cast<ptk::Neighbor*>(d_out), s, n_over);
+      rc = ptkf::radius_traverse(t, d_q, over_list, n_over_max, radius, e, true, nullptr, d_offsets, o, s, n_over);
     }
   } else if (topological(t)) {  // count pass and fill pass both traverse (no capture)
     if (deep_tree(t)) return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
     if (!fill) ws.cap_valid = false;
-    rc = scratch.reserve(reorder ? permutation_scratch_bytes(nq) : 0);
+    rc = order_batch(t, d_q, nq, s, scratch, 0, &perm);
     if (rc != PTK_OK) return rc;
-    uint32_t* perm = nullptr;
-    if (reorder) {
-      rc = make_permutation(t, d_q, nq, s, scratch, &perm);
-      if (rc != PTK_OK) return rc;
-    }
-    rc = ptkf::radius_topo(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets, reinterpret_cast<ptk::Neighbor*>(d_out), s);
+    rc = ptkf::radius_topo(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets, o, s);
   } else if (deep_tree(t)) {  // record stacks spilling to HBM, a few queries per launch, no capture
     if (!fill) ws.cap_valid = false;
-    const DeepPlan plan = deep_plan(t, nq);
-    rc = scratch.reserve(plan.bytes());
-    if (rc != PTK_OK) return rc;
-    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
-    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
-    auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
-    Timer timer(t, s);
-    for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
-      const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
-      uint64_t* c = fill ? nullptr : d_counts + lo;
-      const uint64_t* of = fill ? d_offsets + lo : nullptr;
-      if (nd) {
-        ptk::DevTreeND dev = t->dev_nd;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::radius_nd_deep(t, dev, d_q + lo * t->dim, n, radius, e, fill, c, of, o, s);
-      } else {
-        ptk::DevTree dev = t->dev;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        rc = ptkf::radius_deep(t, dev, d_q + lo * t->dim, n, radius, e, fill, c, of, o, s);
-      }
-      if (rc != PTK_OK) return rc;
-      PTK_HIP(hipGetLastError());
-    }
-    timer.stop(0, fill ? 0 : nq);
+    rc = deep_pieces(t, nq, s, scratch, 0, fill ? 0 : nq, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return radius_deep(t, dev, d_q + lo * t->dim, n, radius, e, fill, fill ? nullptr : d_counts + lo,
+                         fill ? d_offsets + lo : nullptr, o, s);
+    });
   } else {
     // (the long queries of a list pass are handed to wavefronts: ptk_kernels_coopr.hpp)
     const uint32_t far_cap = !fill && !nd && knob_int("radius_lists", 1) != 0 ? radius_cap(t, nq) : 0u;
     const bool capture = !fill && prepare_capture(t, nq, ws, far_cap != 0u);
     const bool lists = capture && !nd && knob_int("radius_lists", 1) != 0;
     if (!fill) ws.cap_valid = false;
-    rc = scratch.reserve((reorder ? permutation_scratch_bytes(nq) : 0) + (lists && far_cap ? radius_coop_scratch_bytes(t, nq) : 0));
+    // (a query costs what it finds: the densest cells to the front of the launch)
+    rc = order_batch(t, d_q, nq, s, scratch, lists && far_cap ? radius_coop_scratch_bytes(t, nq) : 0, &perm,
+                     nd ? 0u : ptk::kCellsDenseFirst);
     if (rc != PTK_OK) return rc;
-    uint32_t* perm = nullptr;
-    if (reorder) {  // (a query costs what it finds: the densest cells to the front of the launch)
-      rc = make_permutation(t, d_q, nq, s, scratch, &perm, nd ? 0u : ptk::kCellsDenseFirst);
-      if (rc != PTK_OK) return rc;
-    }
     if (capture) {
       if (nd) {
         rc = ptkf::radius_nd_capture(t, d_q, perm, nq, radius, e, d_counts, ws.cap, s);
@@ -2082,17 +2008,15 @@ static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, 
         ws.cap_stream = s;
       }
     } else if (nd) {
-      rc = ptkf::radius_nd(t, d_q, nq, radius, e, fill, d_counts, d_offsets, reinterpret_cast<ptk::Neighbor*>(d_out), s, perm);
+      rc = ptkf::radius_nd(t, d_q, nq, radius, e, fill, d_counts, d_offsets, o, s, perm);
     } else {
-      rc = ptkf::radius_traverse(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets,
-                                 reinterpret_cast<ptk::Neighbor*>(d_out), s);
+      rc = ptkf::radius_traverse(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets, o, s);
     }
   }
   if (rc == PTK_OK && fill && sort) {
     Timer timer(t, s);
     const uint32_t blocks = (uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock);
-    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, nq, d_offsets,
-                       reinterpret_cast<ptk::Neighbor*>(d_out));
+    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, nq, d_offsets, o);
     PTK_HIP(hipGetLastError());
     timer.stop(2, 0);
   }
@@ -2129,19 +2053,16 @@ int ptk_search_radius_count(const ptk_tree* t, const float* q, uint64_t nq, floa
   if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  float* d_q = nullptr;
-  uint64_t* d_c = nullptr;
+  DeviceBlock d_q, d_c;
   const size_t qbytes = (size_t)nq * t->dim * sizeof(float);
-  hipError_t he = hipMalloc((void**)&d_q, qbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_c, nq * 8);
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
+  hipError_t he = d_q.alloc(qbytes);
+  if (he == hipSuccess) he = d_c.alloc(nq * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_q.p, q, qbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) {
-    rc = ptk_search_radius_count_device(t, d_q, nq, radius, e, d_c, nullptr);
-    if (rc == PTK_OK) he = hipMemcpy(counts, d_c, nq * 8, hipMemcpyDeviceToHost);
+    rc = ptk_search_radius_count_device(t, d_q.as<float>(), nq, radius, e, d_c.as<uint64_t>(), nullptr);
+    if (rc == PTK_OK) he = hipMemcpy(counts, d_c.p, nq * 8, hipMemcpyDeviceToHost);
   }
   drop_radius_capture(t);
-  if (d_q) (void)hipFree(d_q);
-  if (d_c) (void)hipFree(d_c);
   if (rc != PTK_OK) return rc;
   if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return PTK_OK;
@@ -2157,26 +2078,36 @@ int ptk_search_radius_fill(const ptk_tree* t, const float* q, uint64_t nq, float
   if (total > 0 && out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  float* d_q = nullptr;
-  uint64_t* d_o = nullptr;
-  ptk_neighbor* d_out = nullptr;
+  DeviceBlock d_q, d_o, d_out;
   const size_t qbytes = (size_t)nq * t->dim * sizeof(float);
-  hipError_t he = hipMalloc((void**)&d_q, qbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_o, (nq + 1) * 8);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_out, std::max<uint64_t>(total, 1) * 8);
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(d_o, offsets, (nq + 1) * 8, hipMemcpyHostToDevice);
+  hipError_t he = d_q.alloc(qbytes);
+  if (he == hipSuccess) he = d_o.alloc((nq + 1) * 8);
+  if (he == hipSuccess) he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_q.p, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(d_o.p, offsets, (nq + 1) * 8, hipMemcpyHostToDevice);
   if (he == hipSuccess) {
     drop_radius_capture(t);  // d_q is this call's own copy: whatever was captured belongs to another buffer
-    rc = ptk_search_radius_fill_device(t, d_q, nq, radius, e, d_o, d_out, sort, nullptr);
-    if (rc == PTK_OK && total > 0) he = hipMemcpy(out, d_out, total * 8, hipMemcpyDeviceToHost);
+    rc = ptk_search_radius_fill_device(t, d_q.as<float>(), nq, radius, e, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort,
+                                       nullptr);
+    if (rc == PTK_OK && total > 0) he = hipMemcpy(out, d_out.p, total * 8, hipMemcpyDeviceToHost);
   }
-  if (d_q) (void)hipFree(d_q);
-  if (d_o) (void)hipFree(d_o);
-  if (d_out) (void)hipFree(d_out);
   if (rc != PTK_OK) return rc;
   if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return PTK_OK;
+}
+
+// counts (n + 1, the last one 0) -> offsets (n + 1) on the device, the offsets copied to the host.
+static hipError_t scan_counts(uint64_t* d_c, uint64_t* d_o, uint64_t n, uint64_t* offsets) {
+  size_t tmp_bytes = 0;
+  DeviceBlock tmp;
+  hipError_t he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(),
+                                          (hipStream_t) nullptr);
+  if (he == hipSuccess) he = tmp.alloc(tmp_bytes ? tmp_bytes : 16);
+  if (he == hipSuccess)
+    he = rocprim::exclusive_scan(tmp.p, tmp_bytes, d_c, d_o, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(),
+                                 (hipStream_t) nullptr);
+  if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (n + 1) * 8, hipMemcpyDeviceToHost);
+  return he;
 }
 
 int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radius, float e, int sort,
@@ -2189,49 +2120,36 @@ int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radi
   if (nq == 0) return PTK_OK;
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  float* d_q = nullptr;
-  uint64_t *d_c = nullptr, *d_o = nullptr;
-  ptk_neighbor* d_out = nullptr;
-  void* tmp = nullptr;
+  DeviceBlock d_q, d_c, d_o, d_out;
   const size_t qbytes = (size_t)nq * t->dim * sizeof(float);
-  hipError_t he = hipMalloc((void**)&d_q, qbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_c, (nq + 1) * 8);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_o, (nq + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (nq + 1) * 8);
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
+  hipError_t he = d_q.alloc(qbytes);
+  if (he == hipSuccess) he = d_c.alloc((nq + 1) * 8);
+  if (he == hipSuccess) he = d_o.alloc((nq + 1) * 8);
+  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nq + 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_q.p, q, qbytes, hipMemcpyHostToDevice);
   uint64_t total = 0;
   if (he == hipSuccess) {
-    rc = ptk_search_radius_count_device(t, d_q, nq, radius, e, d_c, nullptr);
+    rc = ptk_search_radius_count_device(t, d_q.as<float>(), nq, radius, e, d_c.as<uint64_t>(), nullptr);
     if (rc == PTK_OK) {
-      size_t tmp_bytes = 0;
-      he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
-                                   (hipStream_t) nullptr);
-      if (he == hipSuccess) he = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
-      if (he == hipSuccess)
-        he = rocprim::exclusive_scan(tmp, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
-                                     (hipStream_t) nullptr);
-      if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (nq + 1) * 8, hipMemcpyDeviceToHost);
+      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nq, offsets);
       if (he == hipSuccess) {
         total = offsets[nq];
-        he = hipMalloc((void**)&d_out, std::max<uint64_t>(total, 1) * 8);
+        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
       }
-      if (he == hipSuccess) rc = ptk_search_radius_fill_device(t, d_q, nq, radius, e, d_o, d_out, sort, nullptr);
+      if (he == hipSuccess)
+        rc = ptk_search_radius_fill_device(t, d_q.as<float>(), nq, radius, e, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort,
+                                           nullptr);
       if (he == hipSuccess && rc == PTK_OK) {
         *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
         if (*out == nullptr) {
           rc = fail(PTK_ERR_NOMEM, "out of memory");
         } else if (total > 0) {
-          he = hipMemcpy(*out, d_out, total * 8, hipMemcpyDeviceToHost);
+          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
         }
       }
     }
   }
   drop_radius_capture(t);
-  if (tmp) (void)hipFree(tmp);
-  if (d_q) (void)hipFree(d_q);
-  if (d_c) (void)hipFree(d_c);
-  if (d_o) (void)hipFree(d_o);
-  if (d_out) (void)hipFree(d_out);
   if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   if (rc != PTK_OK && *out) {
     std::free(*out);
@@ -2240,10 +2158,15 @@ int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radi
   return rc;
 }
 
-// One pass of the box search over device buffers: count (fill == false: d_counts[i] = hits of box i)
+}  // extern "C"
+
+namespace {
+
+// One pass of the box search over device buffers: count (FILL == false: d_counts[i] = hits of box i)
 // or fill (d_offsets = exclusive scan of the counts; row i of d_out in reference traversal order).
-static int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_mx, uint64_t nb, bool fill,
-                           uint64_t* d_counts, const uint64_t* d_offsets, int32_t* d_out, hipStream_t s) {
+template <bool FILL>
+int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_mx, uint64_t nb, uint64_t* d_counts,
+                    const uint64_t* d_offsets, int32_t* d_out, hipStream_t s) {
   int rc = check_search(t, d_mn, nb);
   if (rc != PTK_OK) return rc;
   if (nb > 0 && d_mx == nullptr) return fail(PTK_ERR_INVALID, "null box buffer");
@@ -2268,13 +2191,13 @@ static int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_
   const uint32_t s1_mask = !topo ? 0u : (t->metric.load() == PTK_METRIC_SO2 ? 1u : 4u);
   if (topo && (deep_tree(t) || t->dev.outer == nullptr))
     return fail(PTK_ERR_UNSUPPORTED, "the box search of this topological tree runs on the host members (kd_tree::search_box)");
-  // Boxes in Morton order of their min corners (launch order only; rows stay in the caller's order).
+  // Boxes in Morton order of their min corners (launch order only; rows stay in the caller's order); the boxes of a
+  // deep tree go as they come.
   const bool deep = deep_tree(t);
-  const bool reorder = !deep && want_reorder(t, nb);
-  const DeepPlan plan = deep ? deep_plan(t, nb) : DeepPlan{0, 0};
+  const size_t root_bytes = (size_t)2 * t->dim * sizeof(float) + 512;
   Scratch scratch(t, s);
-  rc = scratch.reserve((reorder ? permutation_scratch_bytes(nb) : 0) + (size_t)2 * t->dim * sizeof(float) + 512 +
-                       (deep ? plan.bytes() : 0));
+  uint32_t* perm = nullptr;
+  rc = deep ? scratch.reserve(root_bytes + deep_plan(t, nb).bytes()) : order_batch(t, d_mn, nb, s, scratch, root_bytes, &perm);
   if (rc != PTK_OK) return rc;
   float* d_root = nullptr;
   if (t->dim > 3) {  // the root box of the any-dimension kernel: min[dim], max[dim]
@@ -2283,101 +2206,62 @@ static int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_
     PTK_HIP(hipMemcpyAsync(d_root, t->root_min.data(), t->dim * sizeof(float), hipMemcpyHostToDevice, s));
     PTK_HIP(hipMemcpyAsync(d_root + t->dim, t->root_max.data(), t->dim * sizeof(float), hipMemcpyHostToDevice, s));
   }
-  uint32_t* perm = nullptr;
-  if (reorder) {
-    rc = make_permutation(t, d_mn, nb, s, scratch, &perm);
-    if (rc != PTK_OK) return rc;
-  }
-  const uint32_t blocks = (uint32_t)((nb + 63) / 64);
   const auto* ranges = static_cast<const uint2*>(t->d_ranges);
-  Timer timer(t, s);
-  if (deep) {  // record stacks spilling to HBM, a few boxes per launch
-    ptk::Record* spill = scratch.take<ptk::Record>((size_t)plan.piece * plan.cap);
-    if (spill == nullptr) return fail(PTK_ERR_NOMEM, "scratch block too small");
-    for (uint64_t lo = 0; lo < nb; lo += plan.piece) {
-      const uint64_t n = std::min<uint64_t>(plan.piece, nb - lo);
-      const uint32_t pb = (uint32_t)((n + 63) / 64);
-      uint64_t* c = fill ? nullptr : d_counts + lo;
-      const uint64_t* of = fill ? d_offsets + lo : nullptr;
-      if (t->dim > 3) {
-        ptk::DevTreeND dev = t->dev_nd;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        if (fill) {
-          rc = allow_lds(ptk::box_nd_kernel<16, -1, true>, nd_smem);
-          if (rc != PTK_OK) return rc;
-          hipLaunchKernelGGL((ptk::box_nd_kernel<16, -1, true>), dim3(pb), dim3(64), nd_smem, s, dev, ranges, d_root,
-                             d_mn + lo * t->dim, d_mx + lo * t->dim, n, c, of, d_out, nullptr);
-        } else {
-          rc = allow_lds(ptk::box_nd_kernel<16, -1, false>, nd_smem);
-          if (rc != PTK_OK) return rc;
-          hipLaunchKernelGGL((ptk::box_nd_kernel<16, -1, false>), dim3(pb), dim3(64), nd_smem, s, dev, ranges, d_root,
-                             d_mn + lo * t->dim, d_mx + lo * t->dim, n, c, of, d_out, nullptr);
+  // The launch of boxes [lo, lo + n) over either tree view; ovf = the spill capacity of the lanes' stacks (-1: in HBM).
+  auto launch = [&](auto ovf, const auto& dev, uint64_t lo, uint64_t n) -> int {
+    constexpr int OVF = decltype(ovf)::value;
+    const dim3 grid((uint32_t)((n + 63) / 64));
+    const float *mn = d_mn + lo * t->dim, *mx = d_mx + lo * t->dim;
+    uint64_t* c = FILL ? nullptr : d_counts + lo;
+    const uint64_t* of = FILL ? d_offsets + lo : nullptr;
+    if constexpr (std::is_same_v<std::decay_t<decltype(dev)>, ptk::DevTreeND>) {
+      const int lrc = allow_lds(ptk::box_nd_kernel<16, OVF, FILL>, nd_smem);
+      if (lrc != PTK_OK) return lrc;
+      hipLaunchKernelGGL((ptk::box_nd_kernel<16, OVF, FILL>), grid, dim3(64), nd_smem, s, dev, ranges, d_root, mn, mx, n, c,
+                         of, d_out, perm);
+    } else {
+      if constexpr (OVF >= 0) {  // (a deep topological tree has been refused above)
+        if (topo) {
+          hipLaunchKernelGGL((ptk::box_kernel<16, OVF, FILL, true>), grid, dim3(64), 16 * 64 * 8, s, dev, ranges, root, mn,
+                             mx, t->dim, n, c, of, d_out, perm, s1_mask);
+          return PTK_OK;
         }
-      } else {
-        ptk::DevTree dev = t->dev;
-        dev.deep_spill = spill;
-        dev.deep_cap = plan.cap;
-        if (fill)
-          hipLaunchKernelGGL((ptk::box_kernel<16, -1, true>), dim3(pb), dim3(64), 16 * 64 * 8, s, dev, ranges, root,
-                             d_mn + lo * t->dim, d_mx + lo * t->dim, t->dim, n, c, of, d_out, nullptr);
-        else
-          hipLaunchKernelGGL((ptk::box_kernel<16, -1, false>), dim3(pb), dim3(64), 16 * 64 * 8, s, dev, ranges, root,
-                             d_mn + lo * t->dim, d_mx + lo * t->dim, t->dim, n, c, of, d_out, nullptr);
       }
-      PTK_HIP(hipGetLastError());
+      hipLaunchKernelGGL((ptk::box_kernel<16, OVF, FILL>), grid, dim3(64), 16 * 64 * 8, s, dev, ranges, root, mn, mx, t->dim,
+                         n, c, of, d_out, perm, 0u);
     }
-  } else if (!fill) {
-    PTK_WITH_OVF(16, ([&]() -> int {
-                   if (t->dim > 3) {
-                     int lrc = allow_lds(ptk::box_nd_kernel<16, OVF, false>, nd_smem);
-                     if (lrc != PTK_OK) return lrc;
-                     hipLaunchKernelGGL((ptk::box_nd_kernel<16, OVF, false>), dim3(blocks), dim3(64), nd_smem, s, t->dev_nd,
-                                        ranges, d_root, d_mn, d_mx, nb, d_counts, nullptr, nullptr, perm);
-                     return PTK_OK;
-                   }
-                   if (topo)
-                     hipLaunchKernelGGL((ptk::box_kernel<16, OVF, false, true>), dim3(blocks), dim3(64), 16 * 64 * 8, s, t->dev,
-                                        ranges, root, d_mn, d_mx, t->dim, nb, d_counts, nullptr, nullptr, perm, s1_mask);
-                   else
-                     hipLaunchKernelGGL((ptk::box_kernel<16, OVF, false>), dim3(blocks), dim3(64), 16 * 64 * 8, s, t->dev,
-                                        ranges, root, d_mn, d_mx, t->dim, nb, d_counts, nullptr, nullptr, perm, 0u);
-                   return PTK_OK;
-                 }()));
-  } else {
-    PTK_WITH_OVF(16, ([&]() -> int {
-                   if (t->dim > 3) {
-                     int lrc = allow_lds(ptk::box_nd_kernel<16, OVF, true>, nd_smem);
-                     if (lrc != PTK_OK) return lrc;
-                     hipLaunchKernelGGL((ptk::box_nd_kernel<16, OVF, true>), dim3(blocks), dim3(64), nd_smem, s, t->dev_nd,
-                                        ranges, d_root, d_mn, d_mx, nb, nullptr, d_offsets, d_out, perm);
-                     return PTK_OK;
-                   }
-                   if (topo)
-                     hipLaunchKernelGGL((ptk::box_kernel<16, OVF, true, true>), dim3(blocks), dim3(64), 16 * 64 * 8, s, t->dev,
-                                        ranges, root, d_mn, d_mx, t->dim, nb, nullptr, d_offsets, d_out, perm, s1_mask);
-                   else
-                     hipLaunchKernelGGL((ptk::box_kernel<16, OVF, true>), dim3(blocks), dim3(64), 16 * 64 * 8, s, t->dev,
-                                        ranges, root, d_mn, d_mx, t->dim, nb, nullptr, d_offsets, d_out, perm, 0u);
-                   return PTK_OK;
-                 }()));
+    return PTK_OK;
+  };
+  const int kind = FILL ? 3 : 0;
+  const uint64_t queries = FILL ? 0 : nb;
+  if (deep) {  // record stacks spilling to HBM, a few boxes per launch
+    return deep_pieces(t, nb, s, scratch, kind, queries, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return launch(std::integral_constant<int, -1>{}, dev, lo, n);
+    });
   }
+  Timer timer(t, s);
+  PTK_WITH_OVF(16, (t->dim > 3 ? launch(std::integral_constant<int, OVF>{}, t->dev_nd, 0, nb)
+                               : launch(std::integral_constant<int, OVF>{}, t->dev, 0, nb)));
   if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
-  timer.stop(fill ? 3 : 0, fill ? 0 : nb);
+  timer.stop(kind, queries);
   return PTK_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int ptk_search_box_count_device(const ptk_tree* t, const float* d_mins, const float* d_maxs, uint64_t nb,
                                 uint64_t* d_counts, void* stream) {
   if (nb > 0 && d_counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
-  return box_pass_device(t, d_mins, d_maxs, nb, false, d_counts, nullptr, nullptr, static_cast<hipStream_t>(stream));
+  return box_pass_device<false>(t, d_mins, d_maxs, nb, d_counts, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int ptk_search_box_fill_device(const ptk_tree* t, const float* d_mins, const float* d_maxs, uint64_t nb,
                                const uint64_t* d_offsets, int32_t* d_out, void* stream) {
   if (nb > 0 && (d_offsets == nullptr || d_out == nullptr)) return fail(PTK_ERR_INVALID, "null offsets / output buffer");
-  return box_pass_device(t, d_mins, d_maxs, nb, true, nullptr, d_offsets, d_out, static_cast<hipStream_t>(stream));
+  return box_pass_device<true>(t, d_mins, d_maxs, nb, nullptr, d_offsets, d_out, static_cast<hipStream_t>(stream));
 }
 
 int ptk_search_box(const ptk_tree* t, const float* mins, const float* maxs, uint64_t nb, uint64_t* offsets,
@@ -2391,51 +2275,37 @@ int ptk_search_box(const ptk_tree* t, const float* mins, const float* maxs, uint
   if (nb == 0) return PTK_OK;
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  float *d_mn = nullptr, *d_mx = nullptr;
-  uint64_t *d_c = nullptr, *d_o = nullptr;
-  int32_t* d_out = nullptr;
-  void* tmp = nullptr;
+  DeviceBlock d_mn, d_mx, d_c, d_o, d_out;
   const size_t bbytes = (size_t)nb * t->dim * sizeof(float);
-  hipError_t he = hipMalloc((void**)&d_mn, bbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_mx, bbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_c, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_o, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemcpy(d_mn, mins, bbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(d_mx, maxs, bbytes, hipMemcpyHostToDevice);
+  hipError_t he = d_mn.alloc(bbytes);
+  if (he == hipSuccess) he = d_mx.alloc(bbytes);
+  if (he == hipSuccess) he = d_c.alloc((nb + 1) * 8);
+  if (he == hipSuccess) he = d_o.alloc((nb + 1) * 8);
+  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nb + 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_mn.p, mins, bbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(d_mx.p, maxs, bbytes, hipMemcpyHostToDevice);
   uint64_t total = 0;
   if (he == hipSuccess) {
-    rc = ptk_search_box_count_device(t, d_mn, d_mx, nb, d_c, nullptr);
+    rc = ptk_search_box_count_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_c.as<uint64_t>(), nullptr);
     if (rc == PTK_OK) {
-      size_t tmp_bytes = 0;
-      he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, nb + 1, rocprim::plus<uint64_t>(),
-                                   (hipStream_t) nullptr);
-      if (he == hipSuccess) he = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
-      if (he == hipSuccess)
-        he = rocprim::exclusive_scan(tmp, tmp_bytes, d_c, d_o, (uint64_t)0, nb + 1, rocprim::plus<uint64_t>(),
-                                     (hipStream_t) nullptr);
-      if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (nb + 1) * 8, hipMemcpyDeviceToHost);
+      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nb, offsets);
       if (he == hipSuccess) {
         total = offsets[nb];
-        he = hipMalloc((void**)&d_out, std::max<uint64_t>(total, 1) * 4);
+        he = d_out.alloc(std::max<uint64_t>(total, 1) * 4);
       }
-      if (he == hipSuccess) rc = ptk_search_box_fill_device(t, d_mn, d_mx, nb, d_o, d_out, nullptr);
+      if (he == hipSuccess)
+        rc = ptk_search_box_fill_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_o.as<uint64_t>(), d_out.as<int32_t>(),
+                                        nullptr);
       if (he == hipSuccess && rc == PTK_OK) {
         *out = static_cast<int32_t*>(std::malloc(std::max<uint64_t>(total, 1) * 4));
         if (*out == nullptr) {
           rc = fail(PTK_ERR_NOMEM, "out of memory");
         } else if (total > 0) {
-          he = hipMemcpy(*out, d_out, total * 4, hipMemcpyDeviceToHost);
+          he = hipMemcpy(*out, d_out.p, total * 4, hipMemcpyDeviceToHost);
         }
       }
     }
   }
-  if (tmp) (void)hipFree(tmp);
-  if (d_mn) (void)hipFree(d_mn);
-  if (d_mx) (void)hipFree(d_mx);
-  if (d_c) (void)hipFree(d_c);
-  if (d_o) (void)hipFree(d_o);
-  if (d_out) (void)hipFree(d_out);
   if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   if (rc != PTK_OK && *out) {
     std::free(*out);
@@ -2607,6 +2477,7 @@ int ptk_debug_batch_permutation(const ptk_tree* t, const float* d_q, uint64_t nq
   if (d_perm == nullptr || nq == 0) return fail(PTK_ERR_INVALID, "null permutation buffer or empty batch");
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  // (not order_batch: the permutation of ANY batch, whatever the handle's reorder mode would do with it)
   Scratch scratch(t, nullptr);
   rc = scratch.reserve(permutation_scratch_bytes(nq));
   if (rc != PTK_OK) return rc;

@@ -257,6 +257,23 @@ struct DeviceGuard {
   }
 };
 
+// A device allocation of one call's own, freed when the call returns.  The host forms of the radius and box searches
+// allocate per call: what they need follows the batch AND its hits, and a handle does not keep blocks of that size.
+struct DeviceBlock {
+  void* p = nullptr;
+  DeviceBlock() = default;
+  DeviceBlock(const DeviceBlock&) = delete;
+  DeviceBlock& operator=(const DeviceBlock&) = delete;
+  ~DeviceBlock() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
 inline int env_int(const char* name, int fallback);  // defined with the launch helpers below
 
 // Host threads for the tree build (the result does not depend on it): PTK_BUILD_THREADS, else the
@@ -453,6 +470,7 @@ class Scratch {
     reserved_ = true;
     return PTK_OK;
   }
+  bool reserved() const { return reserved_; }
   void note_meta(const uint32_t* meta, int kind, uint32_t cap0 = 0, uint32_t cap1 = 0) {
     ws_.last_meta = meta;
     ws_.last_meta_kind = kind;
@@ -584,6 +602,41 @@ inline int check_search(const ptk_tree* t, const void* q, uint64_t nq) {
   return PTK_OK;
 }
 
+// Is the handle's metric one of the topological ones (either precision: both handles keep `metric`)?
+template <class Tree>
+inline bool topological(const Tree* t) {
+  const int m = t->metric.load();
+  return m == PTK_METRIC_SO2 || m == PTK_METRIC_SE2_SQUARED;
+}
+
+// The argument checks of the search entry points: every refusal and its message in one place, and one check per search
+// that its _device form and its host form both call (either precision: check_search has an overload per handle type).
+// A check refuses in the order ptk.h lists the arguments; an empty batch is looked at no further (PTK_OK: the caller
+// returns on `rc != PTK_OK || nq == 0`), so its output buffer may be null.
+inline int check_k(uint32_t k) { return k == 0 ? fail(PTK_ERR_INVALID, "k must be >= 1") : PTK_OK; }
+inline int check_ratio(double e) { return e > 0.0 ? PTK_OK : fail(PTK_ERR_INVALID, "approximation ratio e must be > 0"); }
+inline int check_radius(double radius) {
+  return radius >= 0.0 ? PTK_OK : fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+}
+template <class Tree>
+inline int check_knn_within(const Tree* t, const void* q, uint64_t nq, uint32_t k, double radius, const void* out) {
+  int rc = check_search(t, q, nq);
+  if (rc == PTK_OK) rc = check_k(k);
+  if (rc == PTK_OK) rc = check_radius(radius);
+  if (rc != PTK_OK || nq == 0) return rc;
+  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  return PTK_OK;
+}
+template <class Tree>
+inline int check_count_within(const Tree* t, const void* q, uint64_t nq, double radius, const void* counts) {
+  int rc = check_search(t, q, nq);
+  if (rc == PTK_OK) rc = check_radius(radius);
+  if (rc != PTK_OK || nq == 0) return rc;
+  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  return PTK_OK;
+}
+
 inline float inv_ratio(float e) { return 1.0f / e; }
 
 
@@ -711,10 +764,6 @@ inline uint32_t knn_reg_max(bool) { return 64u; }
   }
 
 // ---- topological metrics (ptk_kernels_topo.hpp) ------------------------------------------------
-inline bool topological(const ptk_tree* t) {
-  const int m = t->metric.load();
-  return m == PTK_METRIC_SO2 || m == PTK_METRIC_SE2_SQUARED;
-}
 #define PTK_WITH_TOPO(CALL)                                         \
   if (t->metric.load() == PTK_METRIC_SO2) {                         \
     using T = ptk::TopoSO2;                                         \

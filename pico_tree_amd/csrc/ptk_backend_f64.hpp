@@ -62,6 +62,15 @@ struct ptk_tree64 {
   mutable size_t io_capacity[2] = {0, 0};
 };
 
+// (an overload of ptkb::check_search in the handle's own namespace: the argument checks of ptk_backend_core.hpp, templates
+// over the handle type, find it there)
+inline int check_search(const ptk_tree64* t, const void* q, uint64_t nq) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  if (nq > 0 && q == nullptr) return fail(PTK_ERR_INVALID, "null query buffer");
+  if (t->device == kDeviceNone) return fail(PTK_ERR_DEVICE, "this handle has no device replica");
+  return PTK_OK;
+}
+
 namespace {
 
 // Stack block of one launch; larger batches go through in pieces (PTK_STACK64_MB shrinks it for tests).
@@ -176,13 +185,6 @@ int finish_create64(ptk_tree64* t, const double* points, int32_t device, ptk_tre
   return PTK_OK;
 }
 
-int check_search64(const ptk_tree64* t, const void* q, uint64_t nq) {
-  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
-  if (nq > 0 && q == nullptr) return fail(PTK_ERR_INVALID, "null query buffer");
-  if (t->device == kDeviceNone) return fail(PTK_ERR_DEVICE, "this handle has no device replica");
-  return PTK_OK;
-}
-
 // A device buffer of a host-buffer call: block `which` of the handle when it fits what a handle keeps, else an allocation
 // of the call's own (freed by the destructor).  The caller holds t->io_mutex.
 constexpr size_t kIoKeepBytes = size_t(64) << 20;
@@ -216,6 +218,30 @@ struct IoBuffer {
   }
 };
 
+// The host-buffer form of a search whose rows have one size: under the handle's I/O lock the batch goes up into block 0,
+// `search(d_q, d_out)` -- the _device form, on the null stream -- fills block 1, and that comes down.  `records`: the rows
+// are ptk_neighbor64 records, whose padding bytes no kernel writes: the block is cleared first.
+template <class Search>
+int host_round_trip64(const ptk_tree64* t, const double* q, uint64_t nq, void* out, size_t out_bytes, bool records,
+                      Search&& search) {
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bq, bo;
+  const size_t qbytes = (size_t)nq * t->dim * sizeof(double);
+  hipError_t he = bq.get(t, 0, qbytes);
+  if (he == hipSuccess) he = bo.get(t, 1, out_bytes);
+  if (he == hipSuccess && records) he = hipMemset(bo.p, 0, out_bytes ? out_bytes : 16);
+  if (he == hipSuccess) he = hipMemcpy(bq.p, q, qbytes, hipMemcpyHostToDevice);
+  int rc = PTK_OK;
+  if (he == hipSuccess) {
+    rc = search(reinterpret_cast<const double*>(bq.p), bo.p);
+    if (rc == PTK_OK) he = hipMemcpy(out, bo.p, out_bytes, hipMemcpyDeviceToHost);
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  return rc;
+}
+
 // Pieces of a batch that fit the stack block; *stack is valid on `s` after the call.
 struct Stack64Lease {
   const ptk_tree64* t;
@@ -225,6 +251,7 @@ struct Stack64Lease {
   Stack64Lease(const ptk_tree64* tree, hipStream_t stream) : t(tree), lock(tree->mutex), s(stream) {}
   uint64_t piece = 0;  // queries per launch
   char* aux = nullptr; // aux_bytes of scratch for the caller (the launch-order permutation)
+  char* own = nullptr; // ... and behind the permutation what the caller asked order_batch64 for beyond it
   ptk::Rec64* stack = nullptr;
   int acquire(uint64_t n, size_t aux_bytes = 0) {
     t->last_meta = nullptr;  // (the aux block is about to be written again: the last capped call's counters go with it)
@@ -305,6 +332,19 @@ int make_permutation64(const ptk_tree64* t, const double* d_q, uint64_t nq, hipS
   if (rc_sort != PTK_OK) return rc_sort;
   *perm = ids_out;
   return PTK_OK;
+}
+
+// The stack block and the launch order of a batch in one call: the lease's pieces and stacks for `nq` rows, its aux block
+// holding the permutation's arrays and, at lease.own, `own_bytes` of the caller's; then the sort (make_permutation64).
+// PTK_ERR_NOMEM comes from the lease alone: a caller that can do without its own bytes asks again with none.
+int order_batch64(const ptk_tree64* t, const double* d_q, uint64_t nq, hipStream_t s, Stack64Lease& lease, size_t own_bytes,
+                  const uint32_t** perm, bool long_first = false) {
+  *perm = nullptr;
+  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
+  const int rc = lease.acquire(nq, perm_bytes + own_bytes);
+  if (rc != PTK_OK) return rc;
+  lease.own = lease.aux + perm_bytes;
+  return make_permutation64(t, d_q, nq, s, lease, perm, long_first);
 }
 
 #define PTK_WITH_METRIC64(CALL)                         \
@@ -700,15 +740,14 @@ int launch_box64(const ptk_tree64* t, const double* d_mins, const double* d_maxs
 // counts (nq + 1, last = 0) -> offsets (nq + 1) on the device, offsets copied to the host.
 int scan_counts64(uint64_t* d_c, uint64_t* d_o, uint64_t nq, uint64_t* offsets) {
   size_t tmp_bytes = 0;
-  void* tmp = nullptr;
+  DeviceBlock tmp;
   hipError_t he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
                                           (hipStream_t) nullptr);
-  if (he == hipSuccess) he = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 16);
+  if (he == hipSuccess) he = tmp.alloc(tmp_bytes ? tmp_bytes : 16);
   if (he == hipSuccess)
-    he = rocprim::exclusive_scan(tmp, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
+    he = rocprim::exclusive_scan(tmp.p, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
                                  (hipStream_t) nullptr);
   if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (nq + 1) * 8, hipMemcpyDeviceToHost);
-  if (tmp) (void)hipFree(tmp);
   if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error in the offsets scan: %s", hipGetErrorString(he));
   return PTK_OK;
 }
@@ -897,11 +936,10 @@ int ptk_tree64_serialize_topological(const ptk_tree64* t, void* buf, uint64_t ca
 
 int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq, uint32_t k, double e,
                             ptk_neighbor64* d_out, void* stream) {
-  int rc = check_search64(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(e > 0.0)) return fail(PTK_ERR_INVALID, "approximation ratio e must be > 0");
-  if (nq == 0) return PTK_OK;
+  int rc = check_search(t, d_q, nq);
+  if (rc == PTK_OK) rc = check_k(k);
+  if (rc == PTK_OK) rc = check_ratio(e);
+  if (rc != PTK_OK || nq == 0) return rc;
   if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(t->device);
@@ -912,22 +950,19 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
   const bool short_tree = k > t->n_points;
   Stack64Lease lease(t, s);
   uint32_t cap = knn64_cap(t, e, nq, k, short_tree);
-  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
-  rc = lease.acquire(nq, perm_bytes + (cap != 0u ? knn64_coop_scratch_bytes(t, nq, k) : 0));
+  const uint32_t* perm = nullptr;
+  rc = order_batch64(t, d_q, nq, s, lease, cap != 0u ? knn64_coop_scratch_bytes(t, nq, k) : 0, &perm, /*long_first=*/true);
   if (rc == PTK_ERR_NOMEM && cap != 0u) {  // (no room for the hand-over list: the uncapped search needs none)
     cap = 0u;
-    rc = lease.acquire(nq, perm_bytes);
+    rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
   }
-  if (rc != PTK_OK) return rc;
-  const uint32_t* perm = nullptr;
-  rc = make_permutation64(t, d_q, nq, s, lease, &perm, /*long_first=*/true);
   if (rc != PTK_OK) return rc;
   if (cap != 0u) {
     if (t->metric.load() == PTK_METRIC_L1)
       return launch_knn64_capped<ptk::Metric64L1>(t, d_q, perm, nq, k, cap, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
-                                                 lease.aux + perm_bytes);
+                                                 lease.own);
     return launch_knn64_capped<ptk::Metric64L2>(t, d_q, perm, nq, k, cap, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
-                                               lease.aux + perm_bytes);
+                                               lease.own);
   }
   PTK_WITH_METRIC64(rc = launch_knn64<M>(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
                                          short_tree));
@@ -939,15 +974,9 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
 // (~2 000 levels), a radius that is subnormal or whose margin overflows.
 int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint64_t nq, uint32_t k, double radius,
                                    ptk_neighbor64* d_out, void* stream) {
-  int rc = check_search64(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (d_out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  int rc = check_knn_within(t, d_q, nq, k, radius, d_out);
+  if (rc != PTK_OK || nq == 0) return rc;
   const int m = t->metric.load();
-  if (m == PTK_METRIC_SO2 || m == PTK_METRIC_SE2_SQUARED)
-    return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
@@ -956,11 +985,8 @@ int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint6
       !std::isfinite(seed))
     seed = 1.7976931348623157e+308;
   Stack64Lease lease(t, s);
-  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
-  rc = lease.acquire(nq, perm_bytes);
-  if (rc != PTK_OK) return rc;
   const uint32_t* perm = nullptr;
-  rc = make_permutation64(t, d_q, nq, s, lease, &perm, /*long_first=*/true);
+  rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
   if (rc != PTK_OK) return rc;
   PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, seed, radius, reinterpret_cast<ptk::Neighbor64*>(d_out),
                                                 s, lease));
@@ -969,29 +995,13 @@ int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint6
 
 int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, double radius,
                             ptk_neighbor64* out) {
-  int rc = check_search64(t, q, nq);
-  if (rc != PTK_OK) return rc;
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bq, bo;
-  const size_t qbytes = (size_t)nq * t->dim * sizeof(double), obytes = (size_t)nq * k * sizeof(ptk_neighbor64);
-  hipError_t he = bq.get(t, 0, qbytes);
-  if (he == hipSuccess) he = bo.get(t, 1, obytes);
-  double* d_q = reinterpret_cast<double*>(bq.p);
-  ptk_neighbor64* d_out = reinterpret_cast<ptk_neighbor64*>(bo.p);
-  if (he == hipSuccess) he = hipMemset(d_out, 0, obytes ? obytes : 16);  // padding bytes of the records
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = ptk_search64_knn_within_device(t, d_q, nq, k, radius, d_out, nullptr);
-    if (rc == PTK_OK) he = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  return rc;
+  const int rc = check_knn_within(t, q, nq, k, radius, out);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return host_round_trip64(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
+                           [&](const double* d_q, char* d_out) {
+                             return ptk_search64_knn_within_device(t, d_q, nq, k, radius,
+                                                                   reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
+                           });
 }
 
 // count_within (ptk.h): dim <= 3 and the four non-topological metrics take count64_within_kernel (the
@@ -1012,11 +1022,8 @@ static int count_table64_of(const ptk_tree64* t, hipStream_t s) {
 
 int ptk_search64_count_within_device(const ptk_tree64* t, const double* d_q, uint64_t nq, double radius, uint64_t max_count,
                                      uint64_t* d_counts, void* stream) {
-  int rc = check_search64(t, d_q, nq);
-  if (rc != PTK_OK) return rc;
-  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (d_counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  int rc = check_count_within(t, d_q, nq, radius, d_counts);
+  if (rc != PTK_OK || nq == 0) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
@@ -1027,11 +1034,8 @@ int ptk_search64_count_within_device(const ptk_tree64* t, const double* d_q, uin
     if (rc != PTK_OK) return rc;
   }
   Stack64Lease lease(t, s);
-  const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
-  rc = lease.acquire(nq, perm_bytes);
-  if (rc != PTK_OK) return rc;
   const uint32_t* perm = nullptr;
-  rc = make_permutation64(t, d_q, nq, s, lease, &perm);
+  rc = order_batch64(t, d_q, nq, s, lease, 0, &perm);
   if (rc != PTK_OK) return rc;
   if (own) {
     const bool shortcut = knob_int("count_shortcut", 1) != 0;
@@ -1048,27 +1052,13 @@ int ptk_search64_count_within_device(const ptk_tree64* t, const double* d_q, uin
 
 int ptk_search64_count_within(const ptk_tree64* t, const double* q, uint64_t nq, double radius, uint64_t max_count,
                               uint64_t* counts) {
-  int rc = check_search64(t, q, nq);
-  if (rc != PTK_OK) return rc;
-  if (!(radius >= 0.0)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  if (nq == 0) return PTK_OK;
-  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bq, bc;
-  const size_t qbytes = (size_t)nq * t->dim * sizeof(double), cbytes = (size_t)nq * sizeof(uint64_t);
-  hipError_t he = bq.get(t, 0, qbytes);
-  if (he == hipSuccess) he = bc.get(t, 1, cbytes);
-  double* d_q = reinterpret_cast<double*>(bq.p);
-  uint64_t* d_c = reinterpret_cast<uint64_t*>(bc.p);
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = ptk_search64_count_within_device(t, d_q, nq, radius, max_count, d_c, nullptr);
-    if (rc == PTK_OK) he = hipMemcpy(counts, d_c, cbytes, hipMemcpyDeviceToHost);
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  return rc;
+  const int rc = check_count_within(t, q, nq, radius, counts);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return host_round_trip64(t, q, nq, counts, (size_t)nq * sizeof(uint64_t), /*records=*/false,
+                           [&](const double* d_q, char* d_out) {
+                             return ptk_search64_count_within_device(t, d_q, nq, radius, max_count,
+                                                                     reinterpret_cast<uint64_t*>(d_out), nullptr);
+                           });
 }
 
 int ptk_tree64_debug_knn_coop_counts(const ptk_tree64* t, uint32_t counts[7]) {
@@ -1092,36 +1082,23 @@ int ptk_tree64_debug_knn_coop_counts(const ptk_tree64* t, uint32_t counts[7]) {
 }
 
 int ptk_search64_knn(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, double e, ptk_neighbor64* out) {
-  int rc = check_search64(t, q, nq);
-  if (rc != PTK_OK) return rc;
-  if (nq == 0) return PTK_OK;
+  // (k and e are looked at by the _device form, behind the output buffer: the order this entry point has always had)
+  const int rc = check_search(t, q, nq);
+  if (rc != PTK_OK || nq == 0) return rc;
   if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bq, bo;
-  const size_t qbytes = (size_t)nq * t->dim * sizeof(double), obytes = (size_t)nq * k * sizeof(ptk_neighbor64);
-  hipError_t he = bq.get(t, 0, qbytes);
-  if (he == hipSuccess) he = bo.get(t, 1, obytes);
-  double* d_q = reinterpret_cast<double*>(bq.p);
-  ptk_neighbor64* d_out = reinterpret_cast<ptk_neighbor64*>(bo.p);
-  if (he == hipSuccess) he = hipMemset(d_out, 0, obytes ? obytes : 16);  // padding bytes of the records
-  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = ptk_search64_knn_device(t, d_q, nq, k, e, d_out, nullptr);
-    if (rc == PTK_OK) he = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  return rc;
+  return host_round_trip64(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
+                           [&](const double* d_q, char* d_out) {
+                             return ptk_search64_knn_device(t, d_q, nq, k, e, reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
+                           });
 }
 
 int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, double radius, double e, int sort,
                         uint64_t* offsets, ptk_neighbor64** out) {
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
   *out = nullptr;
-  int rc = check_search64(t, q, nq);
+  int rc = check_search(t, q, nq);
+  if (rc == PTK_OK) rc = check_ratio(e);
   if (rc != PTK_OK) return rc;
-  if (!(e > 0.0)) return fail(PTK_ERR_INVALID, "approximation ratio e must be > 0");
   offsets[0] = 0;
   if (nq == 0) return PTK_OK;
   DeviceGuard guard(t->device);
@@ -1141,17 +1118,15 @@ int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, doubl
   if (he == hipSuccess) {
     Stack64Lease lease(t, nullptr);
     uint32_t cap = radius64_cap(t, nq);
-    const size_t perm_bytes = (permutation64_bytes(nq) + 255) & ~size_t(255);
-    rc = lease.acquire(nq, perm_bytes + (cap != 0u ? radius64_coop_scratch_bytes(t, nq) : 0));
+    const uint32_t* perm = nullptr;
+    rc = order_batch64(t, d_q, nq, nullptr, lease, cap != 0u ? radius64_coop_scratch_bytes(t, nq) : 0, &perm);
     if (rc == PTK_ERR_NOMEM && cap != 0u) {  // (no room for the hand-over list: the uncapped search needs none)
       cap = 0u;
-      rc = lease.acquire(nq, perm_bytes);
+      rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
     }
-    const uint32_t* perm = nullptr;
-    if (rc == PTK_OK) rc = make_permutation64(t, d_q, nq, nullptr, lease, &perm);
     Radius64Scratch rs;
     if (rc == PTK_OK && cap != 0u) {
-      rs = radius64_carve(t, nq, lease.aux + perm_bytes);
+      rs = radius64_carve(t, nq, lease.own);
       t->last_meta = rs.meta;
       PTK_WITH_EUCLID64(rc = (launch_radius64_capped<M, false>(t, d_q, perm, nq, radius, e, cap, d_c, nullptr, nullptr, nullptr,
                                                               lease, rs)));
@@ -1199,48 +1174,43 @@ int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs
                      int32_t** out) {
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
   *out = nullptr;
-  int rc = check_search64(t, mins, nb);
+  int rc = check_search(t, mins, nb);
   if (rc != PTK_OK) return rc;
   if (nb > 0 && maxs == nullptr) return fail(PTK_ERR_INVALID, "null box buffer");
   offsets[0] = 0;
   if (nb == 0) return PTK_OK;
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  double *d_mn = nullptr, *d_mx = nullptr;
-  uint64_t *d_c = nullptr, *d_o = nullptr;
-  int32_t* d_out = nullptr;
+  DeviceBlock mn, mx, counts, offs, rows;
   const size_t bbytes = (size_t)nb * t->dim * sizeof(double);
-  hipError_t he = hipMalloc((void**)&d_mn, bbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_mx, bbytes);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_c, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMalloc((void**)&d_o, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemcpy(d_mn, mins, bbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipMemcpy(d_mx, maxs, bbytes, hipMemcpyHostToDevice);
+  hipError_t he = mn.alloc(bbytes);
+  if (he == hipSuccess) he = mx.alloc(bbytes);
+  if (he == hipSuccess) he = counts.alloc((nb + 1) * 8);
+  if (he == hipSuccess) he = offs.alloc((nb + 1) * 8);
+  if (he == hipSuccess) he = hipMemset(counts.p, 0, (nb + 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(mn.p, mins, bbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(mx.p, maxs, bbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) {
+    const double *d_mn = mn.as<double>(), *d_mx = mx.as<double>();
+    uint64_t *d_c = counts.as<uint64_t>(), *d_o = offs.as<uint64_t>();
     Stack64Lease lease(t, nullptr);
     rc = lease.acquire(nb);
     if (rc == PTK_OK) rc = launch_box64<false>(t, d_mn, d_mx, nb, d_c, nullptr, nullptr, nullptr, lease);
     if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, nb, offsets);
     if (rc == PTK_OK) {
       const size_t obytes = std::max<uint64_t>(offsets[nb], 1) * sizeof(int32_t);
-      he = hipMalloc((void**)&d_out, obytes);
-      if (he == hipSuccess) rc = launch_box64<true>(t, d_mn, d_mx, nb, nullptr, d_o, d_out, nullptr, lease);
+      he = rows.alloc(obytes);
+      if (he == hipSuccess) rc = launch_box64<true>(t, d_mn, d_mx, nb, nullptr, d_o, rows.as<int32_t>(), nullptr, lease);
       if (he == hipSuccess && rc == PTK_OK) {
         *out = static_cast<int32_t*>(std::malloc(obytes));
         if (*out == nullptr) {
           rc = fail(PTK_ERR_NOMEM, "out of memory");
         } else {
-          he = hipMemcpy(*out, d_out, obytes, hipMemcpyDeviceToHost);
+          he = hipMemcpy(*out, rows.p, obytes, hipMemcpyDeviceToHost);
         }
       }
     }
   }
-  if (d_mn) (void)hipFree(d_mn);
-  if (d_mx) (void)hipFree(d_mx);
-  if (d_c) (void)hipFree(d_c);
-  if (d_o) (void)hipFree(d_o);
-  if (d_out) (void)hipFree(d_out);
   if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   if (rc != PTK_OK && *out) {
     std::free(*out);
