@@ -461,7 +461,28 @@ int ptk_search64_box(const ptk_tree64* tree, const double* mins,
  * k-list is de-duplicated by index and distances are measured in the original
  * space; reflection vectors derive from `seed` instead of std::random_device.
  * Results are approximate by design; quality is recall against the exact
- * kd_tree, not bit-identity with the reference. */
+ * kd_tree, not bit-identity with the reference.
+ *
+ * Limits and contract:
+ *  - k <= 64 (PTK_ERR_INVALID beyond) and dim <= 7072 (the query, its
+ *    reflection, the queue and the path fill the kernel's 64 KiB of LDS;
+ *    PTK_ERR_UNSUPPORTED beyond).
+ *  - A tree may be at most 95 levels deep.  The sliding-midpoint split cannot
+ *    separate coincident points, so a pile of several hundred coincident points
+ *    under a small max_leaf_size (500 copies, leaf 4: 496 levels), or points
+ *    that crowd geometrically towards one value, are refused at creation:
+ *    PTK_ERR_UNSUPPORTED, the message names the tree and its depth.
+ *  - The points must be finite: a NaN or +-Inf coordinate is refused with
+ *    PTK_ERR_INVALID, the message names the first offending point (the same
+ *    check as ptk_tree_create_from_points, made before the device is looked
+ *    up).  A finite point whose reflection overflows (a coordinate near
+ *    FLT_MAX) is refused with PTK_ERR_UNSUPPORTED "tree t: point i ...".
+ *  - A query row with a NaN or +-Inf coordinate, or one whose distances
+ *    overflow (+-FLT_MAX), comes back all padding, {index -1, distance FLT_MAX}
+ *    in every slot, and changes no other row of the batch.  Huge finite rows
+ *    whose squared distances stay finite get ordinary full rows.
+ *  - ptk_forest_get_dropped is cumulative over the life of the handle: every
+ *    search call adds what it dropped, nothing resets it. */
 typedef struct ptk_forest ptk_forest; /* opaque */
 
 int ptk_forest_create(const float* points, uint64_t n_points, uint32_t dim,

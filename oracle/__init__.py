@@ -347,6 +347,8 @@ class ForestOracle:
         fn.argtypes = [c_void_p, c_size_t, c_size_t, c_size_t, c_size_t, c_void_p]
         self._h = fn(self._pts.ctypes.data, n, dim, int(max_leaf_size), rot.shape[0], rot.ctypes.data)
         assert self._h
+        #: Queue entries the last ``search_knn`` call dropped because a per-tree queue (1024 nodes) was full.
+        self.last_dropped = 0
 
     def search_knn(self, q: np.ndarray, k: int, max_leaves_visited: int) -> np.ndarray:
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -355,6 +357,9 @@ class ForestOracle:
         fn.restype = None
         fn.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]
         fn(self._h, q.ctypes.data, len(q), int(k), int(max_leaves_visited), out.ctypes.data)
+        self._lib.ptkor_forest_last_dropped.restype = c_uint64
+        self._lib.ptkor_forest_last_dropped.argtypes = [c_void_p]
+        self.last_dropped = int(self._lib.ptkor_forest_last_dropped(self._h))
         return out
 
     def close(self):

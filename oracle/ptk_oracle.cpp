@@ -785,6 +785,7 @@ struct forest_t {
   std::vector<float> pts;                      // original space
   std::vector<std::vector<float>> rotation;    // per tree
   std::vector<std::unique_ptr<tree_t>> trees;  // over reflected copies
+  std::uint64_t last_dropped = 0;              // queue entries the last search_knn call dropped
 };
 
 void number_nodes(node_t* node, std::uint32_t& next) {
@@ -835,6 +836,7 @@ struct forest_query {
     node_t const* node;
   };
   std::vector<entry> queue;
+  std::uint64_t dropped = 0;  // far children that found the queue full (the product counts the same)
 
   float max() const { return list.size() == k ? list.back().distance : std::numeric_limits<float>::max(); }
 
@@ -874,7 +876,12 @@ struct forest_query {
     }
     descend(t, qr, first, nbd);
     nbd = nbd - old_offset + new_offset;  // :123
-    if (max() > nbd && queue.size() < kForestQueue) queue.push_back({nbd, second});  // :126
+    if (max() > nbd) {  // :126
+      if (queue.size() < kForestQueue)
+        queue.push_back({nbd, second});
+      else
+        ++dropped;
+    }
   }
 
   void search_tree(tree_t const& t, float const* qr, size_t max_leaves) {  // :48-63
@@ -932,9 +939,10 @@ void ptkor_forest_search_knn(void* handle, float const* q, size_t nq, size_t k, 
   auto* f = static_cast<forest_t*>(handle);
   auto* rows = static_cast<neighbor_t*>(out);
   long long const count = static_cast<long long>(nq);
-#pragma omp parallel for schedule(dynamic, 16)
+  std::uint64_t dropped = 0;
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : dropped)
   for (long long i = 0; i < count; ++i) {
-    forest_query s{*f, q + static_cast<size_t>(i) * f->dim, k, {}, {}};
+    forest_query s{*f, q + static_cast<size_t>(i) * f->dim, k, {}, {}, 0};
     std::vector<float> qr(f->dim);
     for (size_t ti = 0; ti < f->trees.size(); ++ti) {
       reflect(f->rotation[ti], s.q, qr.data(), f->dim);
@@ -943,8 +951,13 @@ void ptkor_forest_search_knn(void* handle, float const* q, size_t nq, size_t k, 
     for (size_t j = 0; j < k; ++j)
       rows[static_cast<size_t>(i) * k + j] =
           j < s.list.size() ? s.list[j] : neighbor_t{-1, std::numeric_limits<float>::max()};
+    dropped += s.dropped;
   }
+  f->last_dropped = dropped;
 }
+
+// Far children the last ptkor_forest_search_knn call on this handle could not queue (kForestQueue full).
+std::uint64_t ptkor_forest_last_dropped(void* handle) { return static_cast<forest_t*>(handle)->last_dropped; }
 
 }  // extern "C"
 

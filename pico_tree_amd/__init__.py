@@ -1154,6 +1154,11 @@ class KdForest:
     k > 1, ``search_knn(pts, k, max_leaves_visited)`` (the reference's generic
     ``search_nearest`` with a k-list visitor, de-duplicated by index here).  ``seed`` fixes the
     Householder reflections, which the reference draws from ``std::random_device``.
+
+    Limits (``include/ptk.h``, forest section): ``k <= 64``, ``sdim <= 7072``, trees at most 95 levels deep (several
+    hundred coincident points under a small ``max_leaf_size`` are refused).  The points must be finite, and so must
+    their reflections: :class:`PtkError` otherwise.  A query row that is not finite, or whose distances overflow, comes
+    back all padding ``(-1, FLT_MAX)`` and changes no other row.
     """
 
     def __init__(self, pts, max_leaf_size: int, forest_size: int, seed: int = 0, device: int | None = None):
@@ -1206,7 +1211,8 @@ class KdForest:
 
     @property
     def dropped(self) -> int:
-        """Queue entries dropped so far because a per-tree queue was full (0 in normal use)."""
+        """Queue entries dropped so far because a per-tree queue was full (0 in normal use).  Cumulative over the life
+        of the handle: every search adds what it dropped."""
         v = c_uint64()
         _check(_load().ptk_forest_get_dropped(self._h, byref(v)))
         return int(v.value)

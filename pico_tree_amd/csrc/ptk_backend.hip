@@ -2611,6 +2611,8 @@ int ptk_forest_create(const float* points, uint64_t n_points, uint32_t dim, uint
   if (n_points >= (1ull << 31)) return fail(PTK_ERR_INVALID, "n_points must be < 2^31");
   const size_t lds = ((size_t)2 * dim + 2 * ptk::kForestQueue + 2 * ptk::kForestPath) * 4;
   if (lds > 64 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dimension %u does not fit the forest kernel's LDS", dim);
+  // (as ptk_tree_create_from_points: before the device lookup, so the refusal does not depend on a GPU)
+  if (int rc = check_points_finite(points, n_points, dim); rc != PTK_OK) return rc;
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(PTK_ERR_DEVICE, "no HIP device is visible");
   int dev = device;

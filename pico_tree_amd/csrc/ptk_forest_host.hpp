@@ -70,6 +70,17 @@ inline std::string build_forest_tree(const float* points, uint64_t n, uint32_t d
     for (uint32_t a = 0; a < dim; ++a) dot += r[a] * x[a];
     dot *= 2.0f;
     for (uint32_t a = 0; a < dim; ++a) y[a] = x[a] - (dot * r[a]);
+    // The builder partitions with `<` (std::nth_element), which a NaN makes undefined: a point that is not finite,
+    // or a finite one whose reflection overflows (a coordinate near FLT_MAX), is refused.  (y - y is 0 for every
+    // finite y and NaN for NaN and +-Inf.)
+    float acc = 0.0f;
+    for (uint32_t a = 0; a < dim; ++a) acc += y[a] - y[a];
+    if (!(acc == 0.0f)) {
+      uint32_t a = 0;
+      while (a + 1 < dim && std::isfinite(y[a])) ++a;
+      return "point " + std::to_string(i) + " has no finite reflection (coordinate " + std::to_string(a) + " becomes " +
+             std::to_string(y[a]) + "): a forest is built from finite points whose reflections do not overflow";
+    }
   }
   space_t space(rotated.data(), n, dim);
   internal::space_view<space_t> view(space);
