@@ -604,6 +604,10 @@ int ptk_debug_key_bits(const ptk_tree* tree, uint64_t nq, uint32_t bits[3]);
  * (small batch, PTK_REORDER_OFF), 1 = sorted on the device, 2 = sampled, found coherent and searched in the caller's
  * order (k = 1 under PTK_REORDER_AUTO; the reference's loop walks the rows as given, _pyco_tree/kd_tree.hpp:128-134). */
 int ptk_debug_batch_order(const ptk_tree* tree, int* how);
+/* Launches the last pass of a search made on a tree deeper than the private stack classes (1 032 levels or more: the
+ * record stacks spill to an HBM block of at most PTK_DEEP_SPILL_MB, the batch runs in pieces of at least 64 queries);
+ * 0 if the handle has made no such search. */
+int ptk_debug_deep_pieces(const ptk_tree* tree, uint32_t* pieces);
 
 #ifdef __cplusplus
 } /* extern "C" */

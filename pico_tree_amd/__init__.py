@@ -160,6 +160,7 @@ _SIGNATURES = {
     "ptk_debug_create_phases": (c_int, [c_void_p, POINTER(c_double)]),
     "ptk_debug_key_bits": (c_int, [c_void_p, c_uint64, POINTER(c_uint32)]),
     "ptk_debug_batch_order": (c_int, [c_void_p, POINTER(c_int)]),
+    "ptk_debug_deep_pieces": (c_int, [c_void_p, POINTER(c_uint32)]),
     "ptk_debug_knn_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
     "ptk_debug_radius_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
     "ptk_tree64_debug_knn_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
@@ -769,6 +770,14 @@ class KdTree:
         how = c_int(0)
         _check(_load().ptk_debug_batch_order(self._h, byref(how)))
         return int(how.value)
+
+    def deep_pieces(self) -> int:
+        """Launches of the last pass of a search on a tree deeper than the private stack classes, whose batch runs in
+        pieces (``ptk_debug_deep_pieces``); 0 if there was none."""
+        self._float32_only("deep_pieces()")
+        n = c_uint32(0)
+        _check(_load().ptk_debug_deep_pieces(self._h, byref(n)))
+        return int(n.value)
 
     def key_bits(self, nq: int) -> tuple:
         """Bits of the Morton key per axis for a batch of ``nq`` queries (``ptk_debug_key_bits``)."""

@@ -741,7 +741,8 @@ size_t two_phase_scratch_bytes(const ptk_tree* t, uint64_t nq) {
 uint32_t phase2_cap(float e, uint64_t nq) {
   if (e != 1.0f) return 0;
   const int cap = knob_int("p2_cap", nq >= (4ull << 20) ? 24 : 8);
-  return cap < 0 ? 0u : (uint32_t)cap;
+  // (never above kP2CapMax: what the ring of the capped phase 2 is sized for, ptk_backend_core.hpp)
+  return cap < 0 ? 0u : (uint32_t)std::min(cap, kP2CapMax);
 }
 
 // direct_ids == nullptr: the list is `ho`'s.  Otherwise it is the ranked head of the class-sorted entries, searched
@@ -949,9 +950,9 @@ int dispatch_knn1_of(const ptk_tree* t, const float* d_q, const uint32_t* perm, 
                      ptk::Neighbor* d_out, hipStream_t s, Scratch& scratch) {
   int rc = PTK_OK;
   switch (ovf_class_of(knn1_depth(t), 16)) {  // (the depth of what is traversed: the view without the piles if there is one)
-    case 0: rc = launch_knn1_two_phase<64, M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
-    case 1: rc = launch_knn1_two_phase<256, M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
-    case 2: rc = launch_knn1_two_phase<2048, M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
+    case 0: rc = launch_knn1_two_phase<ptk::kOvfSlots[0], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
+    case 1: rc = launch_knn1_two_phase<ptk::kOvfSlots[1], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
+    case 2: rc = launch_knn1_two_phase<ptk::kOvfSlots[2], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
     default: rc = fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", knn1_depth(t));
   }
   return rc;
@@ -984,12 +985,15 @@ int deep_pieces(const ptk_tree* t, uint64_t nq, hipStream_t s, Scratch& scratch,
   dev_nd.deep_spill = spill;
   dev_nd.deep_cap = plan.cap;
   Timer timer(t, s);
+  uint32_t pieces = 0;
   for (uint64_t lo = 0; lo < nq; lo += plan.piece) {
     const uint64_t n = std::min<uint64_t>(plan.piece, nq - lo);
     const int rc = t->dim > 3 ? launch(dev_nd, lo, n) : launch(dev, lo, n);
     if (rc != PTK_OK) return rc;
     PTK_HIP(hipGetLastError());
+    ++pieces;
   }
+  scratch.note_pieces(pieces);
   timer.stop(kind, queries);
   return PTK_OK;
 }
@@ -2189,7 +2193,9 @@ int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_mx, uin
   // A topological tree: circle axes (metric_so2: axis 0; metric_se2_squared: axis 2), the four-bound tests.
   const bool topo = topological(t);
   const uint32_t s1_mask = !topo ? 0u : (t->metric.load() == PTK_METRIC_SO2 ? 1u : 4u);
-  if (topo && (deep_tree(t) || t->dev.outer == nullptr))
+  if (topo && deep_tree(t))  // (the refusal of the k-NN and radius searches of such a tree, in the same words)
+    return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
+  if (topo && t->dev.outer == nullptr)
     return fail(PTK_ERR_UNSUPPORTED, "the box search of this topological tree runs on the host members (kd_tree::search_box)");
   // Boxes in Morton order of their min corners (launch order only; rows stay in the caller's order); the boxes of a
   // deep tree go as they come.
@@ -2468,6 +2474,13 @@ int ptk_debug_batch_order(const ptk_tree* t, int* how) {
     PTK_HIP(hipMemcpy(&coherent, t->ws.last_verdict, 4, hipMemcpyDeviceToHost));
     if (coherent != 0u) *how = 2;
   }
+  return PTK_OK;
+}
+
+int ptk_debug_deep_pieces(const ptk_tree* t, uint32_t* pieces) {
+  if (t == nullptr || pieces == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  std::lock_guard<std::mutex> lock(t->ws.mutex);
+  *pieces = t->ws.last_deep_pieces;
   return PTK_OK;
 }
 

@@ -40,6 +40,18 @@
 #include "ptk_kernels.hpp"
 // Geometry of the launches (measured optima, profiles/r02_notes.txt item 23, r03_notes.txt item 13):
 constexpr int kP2Ring = 12;   // LDS ring of the capped phase 2 (records per lane; 8 / 10 / 16: 1.335 / 1.329 / 1.308 vs 1.224 ms)
+// The capped phase 2 runs Stack<kP2Ring, OVF> with the OVF of ovf_class_of(depth, 16): four slots fewer than the class
+// was sized for (2 * depth + 2 <= 16 + OVF).  It cannot overflow.  A level of the current root path costs one record
+// while the query went near there and two once it has entered the far child, and a capped traversal enters at most
+// `cap` far children in all (the next one hands the query over), so it never holds more than depth + min(cap, depth)
+// records -- the records phase 1 left (pending ones, RESUME) included.  With cap <= kP2CapMax that is within
+// kP2Ring + OVF for the deepest tree of every class, depth = (16 + OVF - 2) / 2: 39 + 32 <= 76, 135 + 32 <= 268,
+// 1031 + 32 <= 2060.  phase2_cap() (ptk_backend.hip) keeps the test hook p2_cap within kP2CapMax; the shipped caps are
+// 8 and 24.  Measured in the CPU emulator by tests/test_depth_boundaries.py.
+constexpr int kP2CapMax = 32;
+constexpr bool p2_ring_holds(int ovf) { return (16 + ovf - 2) / 2 + kP2CapMax <= kP2Ring + ovf; }
+static_assert(p2_ring_holds(ptk::kOvfSlots[0]) && p2_ring_holds(ptk::kOvfSlots[1]) && p2_ring_holds(ptk::kOvfSlots[2]),
+              "the ring of the capped phase 2 is too small for the spill classes");
 #ifndef PTK_GEN_RING
 #define PTK_GEN_RING 16
 #endif
@@ -126,6 +138,7 @@ struct Workspace {
   // The coherence sample of a batch (ptk::coherence_sample_kernel): its state and verdict stay on the device.
   uint32_t* d_sample = nullptr;             // device (the tail of `base`): {windows counted << 16 | windows failed, verdict}, zero between batches
   const uint32_t* last_verdict = nullptr;   // the verdict word of the last batch on this block, if it was sampled
+  uint32_t last_deep_pieces = 0;  // launches per pass of the last search of a deep tree (deep_pieces, ptk_debug_deep_pieces)
   int last_order = 0;  // the last batch on this block: 0 = taken as it came, 1 = sorted on the device (2 = found coherent
                        // and left alone is only known on the device: last_verdict, ptk_debug_batch_order)
 
@@ -478,6 +491,7 @@ class Scratch {
     ws_.last_meta_cap[1] = cap1;
   }
   void note_order(int how) { ws_.last_order = how; }
+  void note_pieces(uint32_t n) { ws_.last_deep_pieces = n; }
   // The second stream of this scratch block and its two events (made on first use); false if they cannot be had.
   bool side_stream(hipStream_t* side, hipEvent_t* fork, hipEvent_t* join) {
     if (ws_.side == nullptr) {
@@ -524,22 +538,16 @@ class Scratch {
 // Stack geometry: the newest S records of a lane live in an LDS ring, older ones
 // spill to OVF private-scratch slots.  A traversal holds, per level of the current
 // root path, either one pending record (went near, far child unexplored) or two
-// undo records (went far), so 2 * depth + 2 slots always suffice.
-constexpr int kDeepClass = 3;  // deeper than the private classes: spill to HBM, generic kernels only
+// undo records (went far), so 2 * depth + 2 slots always suffice.  The class table itself (ovf_class_of, kOvfSlots,
+// kDeepClass: deeper than the private classes, spill to HBM, generic kernels only) is ptk_kernels.hpp's, beside the stack.
+using ptk::kDeepClass;
+using ptk::ovf_class_of;
 // What a k = 1 search of the default metric traverses: the view without the piles if the tree has any.
 inline const ptk::DevTree& knn1_tree(const ptk_tree* t) { return t->n_piles ? t->dev1 : t->dev; }
 inline const uint2* knn1_ranges(const ptk_tree* t) { return static_cast<const uint2*>(t->n_piles ? t->d_ranges1 : t->d_ranges); }
 inline uint32_t knn1_depth(const ptk_tree* t) { return t->n_piles ? t->max_depth1 : t->max_depth; }
 
-inline int ovf_class_of(uint32_t depth, int s_lds);
 inline int ovf_class(const ptk_tree* t, int s_lds) { return ovf_class_of(t->max_depth, s_lds); }
-inline int ovf_class_of(uint32_t depth, int s_lds) {
-  const uint32_t need = 2 * depth + 2;
-  if (need <= (uint32_t)s_lds + 64) return 0;
-  if (need <= (uint32_t)s_lds + 256) return 1;
-  if (need <= (uint32_t)s_lds + 2048) return 2;
-  return kDeepClass;
-}
 inline bool deep_tree(const ptk_tree* t) { return ovf_class(t, 16) == kDeepClass; }
 
 // A deep tree's launches: `cap` spill records per lane, `piece` queries per launch so that the
@@ -748,9 +756,9 @@ inline uint32_t knn_reg_max(bool) { return 64u; }
 // Runs CALL with OVF bound to the spill capacity the tree's depth needs.
 #define PTK_WITH_OVF(SLDS, CALL)                                                                            \
   switch (ovf_class(t, SLDS)) {                                                                             \
-    case 0: { constexpr int OVF = 64; rc = CALL; } break;                                                   \
-    case 1: { constexpr int OVF = 256; rc = CALL; } break;                                                  \
-    case 2: { constexpr int OVF = 2048; rc = CALL; } break;                                                 \
+    case 0: { constexpr int OVF = ptk::kOvfSlots[0]; rc = CALL; } break;                                    \
+    case 1: { constexpr int OVF = ptk::kOvfSlots[1]; rc = CALL; } break;                                    \
+    case 2: { constexpr int OVF = ptk::kOvfSlots[2]; rc = CALL; } break;                                    \
     default: rc = fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth); \
   }
 

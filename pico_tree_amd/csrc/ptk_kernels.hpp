@@ -224,6 +224,13 @@ __device__ __forceinline__ float point_distance3(float dx, float dy, float dz) {
 // ring (record i at slot i mod S); [0, base) has been spilled (record i at
 // ovf[i]).  S is a power of two.  OVF > 0: that many private slots; OVF == 0: no spill (the ring
 // always suffices); OVF < 0: the spill slots are in HBM (PTK_STACK, DevTree::deep_spill).
+//
+// PTK_STACK_HIGH_WATER(records): a hook of the CPU emulator (tests/cpp/emulate_kernels.cpp defines it before it includes
+// this file, nothing else does), told the number of records on the stack after every push; it expands to nothing in
+// the library.
+#ifndef PTK_STACK_HIGH_WATER
+#define PTK_STACK_HIGH_WATER(records)
+#endif
 template <int S, int OVF, int BLOCK>
 struct Stack {
   static_assert(S >= 4, "ring too small");
@@ -255,6 +262,7 @@ struct Stack {
     rec.y = __float_as_uint(val);
     lds[slot(top) * BLOCK] = pack_record(rec);
     ++top;
+    PTK_STACK_HIGH_WATER(top);
   }
   static constexpr int kUnwind = 8;  // records examined per turn (4 / 12: slower, profiles/r03_notes.txt item 13)
   // The newest records, rr[0] the newest; returns how many are valid (>= 1 unless empty).  They
@@ -311,6 +319,21 @@ struct Stack {
   Stack<S, OVF, BLOCK> st;                                                                                  \
   st.init((LdsWord*)ptk_smem, threadIdx.x,                                                                  \
           (OVF) < 0 ? (TREE).deep_spill + ((uint64_t)blockIdx.x * (BLOCK) + threadIdx.x) * (TREE).deep_cap : spill_)
+
+// The host's choice of OVF (host code; here, beside the stack, so that the CPU emulator checks the same table --
+// tests/test_depth_boundaries.py).  A traversal holds, per level of the current root path, either one pending record
+// (went near, far child unexplored) or two undo records (went far), so 2 * depth + 2 slots always suffice: the
+// smallest class whose S + OVF slots hold that many, or kDeepClass (deeper than the private classes: the records spill
+// to HBM, generic kernels only).
+constexpr int kOvfSlots[3] = {64, 256, 2048};
+constexpr int kDeepClass = 3;
+inline int ovf_class_of(uint32_t depth, int s_lds) {
+  const uint32_t need = 2 * depth + 2;
+  if (need <= (uint32_t)s_lds + (uint32_t)kOvfSlots[0]) return 0;
+  if (need <= (uint32_t)s_lds + (uint32_t)kOvfSlots[1]) return 1;
+  if (need <= (uint32_t)s_lds + (uint32_t)kOvfSlots[2]) return 2;
+  return kDeepClass;
+}
 
 // ---- result policies ------------------------------------------------------------
 // max()  : current pruning distance            visit(): one measured point

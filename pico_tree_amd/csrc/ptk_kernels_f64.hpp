@@ -202,6 +202,7 @@ struct Stack64 {
     rm[(top & (S - 1)) * 64] = meta;
     rv[(top & (S - 1)) * 64] = val;
     ++top;
+    PTK_STACK_HIGH_WATER(top);  // (the emulator's hook: ptk_kernels.hpp, "record stack")
   }
   __device__ __forceinline__ Rec64 pop() {
     if (top == base) {  // ring empty, spilled records remain: bring a batch back

@@ -23,6 +23,12 @@ thread_local dim3 blockDim;
 #include <string>
 #include <vector>
 
+// The record stacks of the kernels (Stack of ptk_kernels.hpp, Stack64 of ptk_kernels_f64.hpp) report the number of
+// records they hold after every push: emu_stack_high_water() below is the largest since the last reset.  Only this
+// unit defines the hook; the library compiles it away.
+void emu_note_stack(int records);
+#define PTK_STACK_HIGH_WATER(records) emu_note_stack(records)
+
 #include "ptk.h"
 #include "ptk_encode.hpp"
 #include "ptk_kernels.hpp"
@@ -42,6 +48,27 @@ thread_local dim3 blockDim;
 
 namespace ptk {
 unsigned char ptk_smem[192 * 1024] __attribute__((aligned(16)));
+}
+
+// ---- high water of the record stacks (PTK_STACK_HIGH_WATER above) -------------------------------
+static int g_stack_high = 0;     // the most records any stack has held since the last reset
+static int g_last_p2_high = 0;   // ... any stack of the phase 2 launch of the last emu_knn1_two_phase call
+static uint32_t g_p2_cap = 0;    // emu_set_p2_cap: the cap of the capped variants of emu_knn1_two_phase (0: the variant's own)
+void emu_note_stack(int records) {
+  if (records > g_stack_high) g_stack_high = records;
+}
+extern "C" {
+int emu_stack_high_water(int reset) {
+  const int v = g_stack_high;
+  if (reset) g_stack_high = 0;
+  return v;
+}
+int emu_last_p2_high_water() { return g_last_p2_high; }
+void emu_set_p2_cap(uint32_t cap) { g_p2_cap = cap; }
+// The host's class table (ptk_kernels.hpp): the class of a depth for a ring of s_lds records, the private spill slots
+// of a class (-1: the deep class, the records spill to HBM).
+int emu_ovf_class(uint32_t depth, int s_lds) { return ptk::ovf_class_of(depth, s_lds); }
+int emu_ovf_slots(int cls) { return cls >= 0 && cls < ptk::kDeepClass ? ptk::kOvfSlots[cls] : -1; }
 }
 
 // ---- wave-level rendezvous for kernels that use __ballot ---------------------------------
@@ -983,7 +1010,8 @@ int emu_knn1_two_phase_m(void* h, const float* q, uint64_t nq, float e, const ui
     ptk::knn1_phase_meta_kernel(sorted_key.data(), (uint32_t)nq, cont, tiers, top_extra);
   }
   const uint32_t blocks = (uint32_t)((nq + 63) / 64) + 1 + top_extra;
-  const uint32_t cap = (variant == 5 || variant == 9) ? 2u : (variant == 6 || variant == 7) ? 1u : variant == 8 ? 3u : 0u;
+  const uint32_t own_cap = (variant == 5 || variant == 9) ? 2u : (variant == 6 || variant == 7) ? 1u : variant == 8 ? 3u : 0u;
+  const uint32_t cap = own_cap != 0u && g_p2_cap != 0u ? g_p2_cap : own_cap;  // (emu_set_p2_cap)
   std::vector<uint32_t> heavy_list(nq, 0xEEEEEEEEu), redo_list(nq, 0xEEEEEEEEu), ntasks(nq, 0xEEEEEEEEu);
   // Room for the stacks of two thirds of the queries handed over at most: the rest starts from the root.
   const uint32_t max_heavy = variant == 6 ? 0u : (uint32_t)(nq / 6 + 1);
@@ -1004,6 +1032,8 @@ int emu_knn1_two_phase_m(void* h, const float* q, uint64_t nq, float e, const ui
   }
   gridDim.x = blocks;
   blockDim.x = 64;
+  const int high_before = g_stack_high;  // (the high water of this launch alone: emu_last_p2_high_water)
+  g_stack_high = 0;
   for (uint32_t b = 0; b < blocks; ++b) {
     blockIdx.x = b;
     for (uint32_t l = 0; l < 64; ++l) {
@@ -1016,6 +1046,8 @@ int emu_knn1_two_phase_m(void* h, const float* q, uint64_t nq, float e, const ui
         ptk::knn1_phase2_kernel<12, 2048, 4, M>(t->dev, qs.data(), e_inv, o, cont, sorted.data(), cap, ho);
     }
   }
+  g_last_p2_high = g_stack_high;
+  g_stack_high = std::max(g_stack_high, high_before);
   g_last_heavy = meta[ptk::kMetaHeavy] + direct_listed;
   g_last_redo = 0;
   if (cap) {
@@ -1314,6 +1346,7 @@ void* emu64_create(const double* points, uint64_t n, uint32_t dim, uint64_t max_
   return e;
 }
 void emu64_destroy(void* h) { delete static_cast<Emu64*>(h); }
+uint32_t emu64_max_depth(void* h) { return static_cast<Emu64*>(h)->st.max_depth; }
 void emu64_set_metric(void* h, int metric) { static_cast<Emu64*>(h)->metric = metric; }
 
 // The kd_tree::save stream of the tree (pico_tree/internal/stream.hpp); returns its size.

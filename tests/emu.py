@@ -31,6 +31,29 @@ def _lib():
     return lib
 
 
+def stack_high_water(reset=True, lib=None):
+    """The most records any record stack of the emulated kernels (``Stack``, ``Stack64``) has held since the last
+    reset, counted in ``push`` itself; ``lib``: another library built around tests/cpp/emulate_kernels.cpp (each has a
+    counter of its own)."""
+    lib = lib or _lib()
+    lib.emu_stack_high_water.restype = c_int
+    lib.emu_stack_high_water.argtypes = [c_int]
+    return int(lib.emu_stack_high_water(int(reset)))
+
+
+def ovf_capacity(depth, ring=16):
+    """Records a stack of `ring` LDS slots holds in the spill class the HOST picks for a tree of that depth
+    (``ovf_class_of`` / ``kOvfSlots`` of ptk_kernels.hpp); None for the deep class, whose spill block in HBM is sized
+    from the depth itself."""
+    lib = _lib()
+    lib.emu_ovf_class.restype = c_int
+    lib.emu_ovf_class.argtypes = [c_uint32, c_int]
+    lib.emu_ovf_slots.restype = c_int
+    lib.emu_ovf_slots.argtypes = [c_int]
+    slots = int(lib.emu_ovf_slots(lib.emu_ovf_class(int(depth), int(ring))))
+    return None if slots < 0 else int(ring) + slots
+
+
 class EmulatedTree:
     """Builds the flat tree with the PRODUCT builder (host-only libptk handle),
     encodes it with the product encoder and runs the product kernels on the CPU."""
@@ -193,13 +216,27 @@ class EmulatedTree:
         self._piles = int(n)
         return self._piles
 
-    def two_phase_knn1(self, q, e=None, perm=None, variant=5):
-        """Returns (result (nq,1), number of continuations handed to phase 2)."""
+    def max_depth(self):
+        """Depth of the encoded tree (of its k = 1 view after ``use_pile_view``)."""
+        return int(self.lib.emu_max_depth(self.h))
+
+    def two_phase_knn1(self, q, e=None, perm=None, variant=5, p2_cap=None):
+        """Returns (result (nq,1), number of continuations handed to phase 2).  ``p2_cap``: far children a query of a
+        capped variant may enter in phase 2 instead of the variant's own 1 - 3; ``last_p2_high_water`` = the most
+        records a stack of that phase 2 launch held."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         out = np.zeros((len(q), 1), dtype=pt.NEIGHBOR)
-        n2 = self.lib.emu_knn1_two_phase(self.h, q.ctypes.data, len(q), e or 1.0,
-                                         perm.ctypes.data if perm is not None else None, variant,
-                                         out.ctypes.data)
+        self.lib.emu_set_p2_cap.argtypes = [c_uint32]
+        self.lib.emu_set_p2_cap.restype = None
+        self.lib.emu_last_p2_high_water.restype = c_int
+        self.lib.emu_set_p2_cap(int(p2_cap or 0))
+        try:
+            n2 = self.lib.emu_knn1_two_phase(self.h, q.ctypes.data, len(q), e or 1.0,
+                                             perm.ctypes.data if perm is not None else None, variant,
+                                             out.ctypes.data)
+        finally:
+            self.lib.emu_set_p2_cap(0)
+        self.last_p2_high_water = int(self.lib.emu_last_p2_high_water())
         assert n2 >= 0
         if getattr(self, "_piles", 0):
             self.lib.emu_resolve_piles.restype = None
@@ -317,6 +354,11 @@ class EmulatedTree64:
         if getattr(self, "h", None):
             self.lib.emu64_destroy(self.h)
             self.h = None
+
+    def max_depth(self):
+        self.lib.emu64_max_depth.restype = c_uint32
+        self.lib.emu64_max_depth.argtypes = [c_void_p]
+        return int(self.lib.emu64_max_depth(self.h))
 
     def save_bytes(self) -> bytes:
         size = self.lib.emu64_save(self.h, None, 0)

@@ -18,6 +18,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
+from tests import depth_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -181,6 +182,35 @@ def test_emulated_kernel_equals_the_reference(emu_count, kind, metric):
         assert np.array_equal(off, want), (kind, metric, r)
     # the large radii take both shortcuts
     assert fired[0] > 0 and fired[1] > 0, fired
+
+
+@needs_reference
+@pytest.mark.parametrize("depth", [39, 40, 135, 136])
+@pytest.mark.parametrize("dim,leaf,metric", [c for c in depth_cases.EUCLID_CASES if c[0] <= 3])
+def test_emulated_kernel_where_the_stack_class_changes(emu_count, dim, leaf, metric, depth):
+    """The CPU half of tests/test_depth_boundaries.py for the count kernel (here, where its emulator is built): trees of
+    exactly 39 | 40 and 135 | 136 levels, queries that fill the record stacks, the radius at the distance of the pile
+    exactly (out: the test is strict), the next number above it (in) and 0; with and without max_count.  Counts of the
+    reference, and no stack above 2 * depth + 2 records nor above what the host's spill class for the depth holds."""
+    pts, pile = depth_cases.cloud_at_depth(depth, dim, leaf)
+    q, _ = depth_cases.queries(pts, pile)
+    ref = oracle.Oracle(pts, leaf, "reference", metric=metric)
+    run = depth_cases.Watch(depth, emu_count)
+    at_corner, peak = [], 0
+    for r in depth_cases.edge_radii(ref, q):
+        want = expected(ref, q, np.float32(r))
+        at_corner.append(int(want[0]))
+        for mc in (0, 16):
+            got, _ = run(emu_counts, emu_count, np.asarray(pts), leaf, metric, q, r, mc)
+            assert np.array_equal(got, np.minimum(want, mc) if mc else want), (r, mc)
+        got, _ = run(emu_counts, emu_count, np.asarray(pts), leaf, metric, q, r, 0, shortcut=0)
+        assert np.array_equal(got, want), (r, "no shortcut")
+        peak = max(peak, run.high)
+    if metric in ("L2Squared", "L1"):
+        # (the sum metrics: the pile is out at r and in just above it, and the corner queries walk the whole chain; under
+        # the max and min metrics the traversal prunes by a SUM over the axes, as the reference's does)
+        assert at_corner == [0, len(pts) - 3_000, 0, len(pts)], at_corner
+        assert depth_cases.need(depth) - peak <= 8, peak
 
 
 @needs_reference

@@ -20,6 +20,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
+from tests import depth_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -200,6 +201,31 @@ def test_emulated_bounded_kernels_equal_the_filtered_reference(emu_within, kind,
             for form in ((0, 1, 2) if k <= 64 else (1, 2)):
                 got = emu_rows(emu_within, p, leaf, metric, q, k, r, form)
                 assert got.tobytes() == want.tobytes(), (kind, metric, k, r, form)
+
+
+@needs_reference
+@pytest.mark.parametrize("depth", [39, 40, 135, 136])
+@pytest.mark.parametrize("dim,leaf,metric", depth_cases.EUCLID_CASES)
+def test_emulated_bounded_kernels_where_the_stack_class_changes(emu_within, dim, leaf, metric, depth):
+    """The CPU half of tests/test_depth_boundaries.py for these kernels (here, where their emulator is built): trees of
+    exactly 39 | 40 and 135 | 136 levels, queries that fill the record stacks, the radius at the distance of the pile
+    exactly (out: the test is strict), the next number above it (in) and 0.  Rows of the filtered reference, and no
+    stack above 2 * depth + 2 records nor above what the host's spill class for the depth holds."""
+    pts, pile = depth_cases.cloud_at_depth(depth, dim, leaf)
+    q, _ = depth_cases.queries(pts, pile)
+    ref = oracle.Oracle(pts, leaf, "reference", metric=metric)
+    run = depth_cases.Watch(depth, emu_within)
+    peak = 0
+    for r in depth_cases.edge_radii(ref, q):
+        for k in (5, 80):
+            want = expected(ref, q, k, r)
+            for form in ((0, 1, 2) if k <= 64 else (1, 2)):
+                got = run(emu_rows, emu_within, np.asarray(pts), leaf, metric, q, k, r, form)
+                assert got.tobytes() == want.tobytes(), (k, r, form)
+                peak = max(peak, run.high)
+    if metric in ("L2Squared", "L1"):
+        # (the sum metrics: the corner queries walk the whole chain; the last radius, 1e4, reaches the cloud as well)
+        assert depth_cases.need(depth) - peak <= 8, peak
 
 
 # ---- the C++ members (tests/cpp/knn_within_main.cpp) ----------------------------------------------------------------
