@@ -213,6 +213,14 @@ struct ptk_api<float> {
                           std::uint64_t* counts) {
     return ptk_search_count_within(t, q, nq, r, max_count, counts);
   }
+  static int knn_within_radii(tree const* t, float const* q, std::uint64_t nq, std::uint32_t k, float const* radii,
+                              neighbor* out) {
+    return ptk_search_knn_within_radii(t, q, nq, k, radii, out);
+  }
+  static int count_within_radii(tree const* t, float const* q, std::uint64_t nq, float const* radii,
+                                std::uint64_t max_count, std::uint64_t* counts) {
+    return ptk_search_count_within_radii(t, q, nq, radii, max_count, counts);
+  }
   static int radius(tree const* t, float const* q, std::uint64_t nq, float r, float e, int sort,
                     std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius(t, q, nq, r, e, sort, offsets, out);
@@ -237,6 +245,14 @@ struct ptk_api<double> {
   static int count_within(tree const* t, double const* q, std::uint64_t nq, double r, std::uint64_t max_count,
                           std::uint64_t* counts) {
     return ptk_search64_count_within(t, q, nq, r, max_count, counts);
+  }
+  static int knn_within_radii(tree const* t, double const* q, std::uint64_t nq, std::uint32_t k, double const* radii,
+                              neighbor* out) {
+    return ptk_search64_knn_within_radii(t, q, nq, k, radii, out);
+  }
+  static int count_within_radii(tree const* t, double const* q, std::uint64_t nq, double const* radii,
+                                std::uint64_t max_count, std::uint64_t* counts) {
+    return ptk_search64_count_within_radii(t, q, nq, radii, max_count, counts);
   }
   static int radius(tree const* t, double const* q, std::uint64_t nq, double r, double e, int sort,
                     std::uint64_t* offsets, neighbor** out) {

@@ -328,6 +328,33 @@ class kd_tree {
     batched_count_within(queries, radius, counts, max_count);
   }
 
+  //! A radius per query row: row i of \p out is row i of the member above
+  //! with radius = radii[i] (padded with {-1, radii[i]}); radii.size() must be
+  //! the number of queries (std::invalid_argument otherwise), every entry >= 0
+  //! and not NaN.  Served by the backend where the scalar form is; where it
+  //! refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined (no backend linked), by a loop over the
+  //! single-query member.
+  template <typename QuerySpace_>
+  inline void search_knn_within(
+      QuerySpace_ const& queries,
+      size_type const k,
+      std::vector<scalar_type> const& radii,
+      neighbor_type* out) const {
+    batched_knn_within_radii(queries, k, radii, out);
+  }
+
+  //! counts[i] = count_within(query i, radii[i]), clamped to \p max_count when
+  //! that is > 0; \p radii as above.
+  template <typename QuerySpace_>
+  inline void count_within(
+      QuerySpace_ const& queries,
+      std::vector<scalar_type> const& radii,
+      size_type* counts,
+      size_type const max_count = 0) const {
+    batched_count_within_radii(queries, radii, counts, max_count);
+  }
+
   //! out[i] = all neighbours of query i within \p radius.
   template <typename QuerySpace_>
   inline void search_radius(
@@ -577,6 +604,81 @@ class kd_tree {
         counts[i] = max_count != 0 && n > max_count ? max_count : n;
       });
     }
+  }
+
+  void check_radii(std::vector<scalar_type> const& radii, size_type rows) const {
+    if (radii.size() != rows) {
+      throw std::invalid_argument("pico_tree: radii must hold one radius per query");
+    }
+  }
+
+  template <typename QuerySpace_>
+  void batched_knn_within_radii(
+      QuerySpace_ const& queries, size_type k, std::vector<scalar_type> const& radii, neighbor_type* out) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    check_radii(radii, q.rows());
+    // (the scalar member's loop with the row's own radius)
+    auto const rows_loop = [&]() {
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(q.rows(), [&](size_type i) {
+        row_point x = make_row(q.data() + i * q.cols(), q.cols());
+        std::vector<neighbor_type> row;
+        search_knn_within(x, k, radii[i], row);
+        std::copy(row.begin(), row.end(), out + i * k);
+        std::fill(out + i * k + row.size(), out + (i + 1) * k, neighbor_type(index_type(-1), radii[i]));
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(
+          api::knn_within_radii(
+              device(), q.data(), q.rows(), static_cast<std::uint32_t>(k), radii.data(),
+              reinterpret_cast<typename api::neighbor*>(out)),
+          "ptk_search_knn_within_radii");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  template <typename QuerySpace_>
+  void batched_count_within_radii(
+      QuerySpace_ const& queries, std::vector<scalar_type> const& radii, size_type* counts, size_type max_count) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    check_radii(radii, q.rows());
+    auto const rows_loop = [&]() {
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(q.rows(), [&](size_type i) {
+        row_point x = make_row(q.data() + i * q.cols(), q.cols());
+        size_type const n = count_within(x, radii[i]);
+        counts[i] = max_count != 0 && n > max_count ? max_count : n;
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    std::vector<std::uint64_t> c(q.rows());
+    try {
+      internal::ptk_check(
+          api::count_within_radii(
+              device(), q.data(), q.rows(), radii.data(), static_cast<std::uint64_t>(max_count), c.data()),
+          "ptk_search_count_within_radii");
+      std::copy(c.begin(), c.end(), counts);
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
   }
 
   //! Row i of a dense query matrix as a point.

@@ -287,6 +287,36 @@ int ptk_search_count_within(const ptk_tree* tree, const float* queries, uint64_t
 int ptk_search_count_within_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, float radius,
                                    uint64_t max_count, uint64_t* d_counts, void* stream);
 
+/* ---- a radius per query row ---------------------------------------------- */
+
+/* ptk_search_knn_within and ptk_search_count_within with `radii`, nq entries: entry i bounds query row i, in the
+ * caller's order (max_count stays one value per call).  Results contract: row i / counts[i] is, bit for
+ * bit, row i / counts[i] of the scalar call on the same batch with radius = radii[i] -- the reference's
+ * search_knn(q_i, min(k, n_points)) row filtered with the strict `< radii[i]` and padded with {-1, radii[i]}; the length
+ * of the reference's search_radius(q_i, radii[i]) row, clamped to max_count.  No row's radius changes another row: a
+ * warm-started ICP iteration passes each row the distance its last iteration found, and no row's search reaches (much)
+ * past its own.
+ * Arguments: the scalar form's checks, and a null `radii` with nq > 0 is PTK_ERR_INVALID.  The host-buffer forms scan
+ * `radii`: a NaN or negative entry is PTK_ERR_INVALID, and ptk_last_error names the first such row.  The _device forms
+ * only enqueue (d_radii is device memory on the tree's device, ordered on `stream` like d_queries) and cannot look at
+ * the values: there a row whose radius is NaN or negative is all padding {-1, radii[i]} (its count is 0), every other
+ * row is what it would be without that row, and the call returns PTK_OK.  +inf, FLT_MAX, 0 and subnormal radii are
+ * valid per row and give what the scalar call gives for them.
+ * Where the device serves them: ptk_search_knn_within_radii wherever the scalar form is served (every dimension, trees
+ * of the deep stack class included; topological metrics PTK_ERR_UNSUPPORTED).  ptk_search_count_within_radii by the
+ * side-table count kernel only -- dim <= 3, the four non-topological metrics, not the deep stack class; dim > 3,
+ * topological metrics and deep trees, which the scalar call sends through the count pass of the radius search (one
+ * radius per launch), are PTK_ERR_UNSUPPORTED for now (ptk_host_search_count_within_radii serves them).
+ * The first count of either kind builds the handle's side table. */
+int ptk_search_knn_within_radii(const ptk_tree* tree, const float* queries, uint64_t nq, uint32_t k, const float* radii,
+                                ptk_neighbor* out);
+int ptk_search_knn_within_radii_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, uint32_t k,
+                                       const float* d_radii, ptk_neighbor* d_out, void* stream);
+int ptk_search_count_within_radii(const ptk_tree* tree, const float* queries, uint64_t nq, const float* radii,
+                                  uint64_t max_count, uint64_t* counts);
+int ptk_search_count_within_radii_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, const float* d_radii,
+                                         uint64_t max_count, uint64_t* d_counts, void* stream);
+
 /* ---- radius search (ragged output) ------------------------------------ */
 
 /* Pass 1: counts[i] = number of points with distance < radius (strict,
@@ -356,6 +386,11 @@ int ptk_host_search_knn_within(const ptk_tree* tree, const float* points, const 
                                uint32_t k, float radius, ptk_neighbor* out);
 int ptk_host_search_count_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
                                  float radius, uint64_t max_count, uint64_t* counts);
+/* (the scalar loops with the row's own radius: radii has nq entries, a NaN or negative one is PTK_ERR_INVALID by its row) */
+int ptk_host_search_knn_within_radii(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
+                                     uint32_t k, const float* radii, ptk_neighbor* out);
+int ptk_host_search_count_within_radii(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
+                                       const float* radii, uint64_t max_count, uint64_t* counts);
 int ptk_host_search_radius(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
                            float e, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
@@ -440,6 +475,17 @@ int ptk_search64_count_within(const ptk_tree64* tree, const double* queries, uin
                               uint64_t max_count, uint64_t* counts);
 int ptk_search64_count_within_device(const ptk_tree64* tree, const double* d_queries, uint64_t nq, double radius,
                                      uint64_t max_count, uint64_t* d_counts, void* stream);
+/* As ptk_search_knn_within_radii / ptk_search_count_within_radii and their _device forms: radii in double, the pad
+ * {-1, radii[i]}; the count form serves dim <= 3 with the four non-topological metrics (float64 trees have no deep
+ * stack class) and refuses the rest with PTK_ERR_UNSUPPORTED. */
+int ptk_search64_knn_within_radii(const ptk_tree64* tree, const double* queries, uint64_t nq, uint32_t k,
+                                  const double* radii, ptk_neighbor64* out);
+int ptk_search64_knn_within_radii_device(const ptk_tree64* tree, const double* d_queries, uint64_t nq, uint32_t k,
+                                         const double* d_radii, ptk_neighbor64* d_out, void* stream);
+int ptk_search64_count_within_radii(const ptk_tree64* tree, const double* queries, uint64_t nq, const double* radii,
+                                    uint64_t max_count, uint64_t* counts);
+int ptk_search64_count_within_radii_device(const ptk_tree64* tree, const double* d_queries, uint64_t nq,
+                                           const double* d_radii, uint64_t max_count, uint64_t* d_counts, void* stream);
 /* As ptk_search_radius: *out is malloc'ed by the library (ptk_free).  With
  * sort != 0 rows ascend by distance, equal distances by index. */
 int ptk_search64_radius(const ptk_tree64* tree, const double* queries,

@@ -100,6 +100,10 @@ _SIGNATURES = {
     "ptk_search_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p]),
     "ptk_search_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
     "ptk_search_count_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p, c_void_p]),
+    "ptk_search_knn_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "ptk_search_knn_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "ptk_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
+    "ptk_search_count_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_count": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p]),
     "ptk_search_radius_fill": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p,
                                        c_void_p, c_int]),
@@ -117,6 +121,8 @@ _SIGNATURES = {
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
+    "ptk_host_search_knn_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "ptk_host_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_float, c_int,
                                        c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -140,6 +146,10 @@ _SIGNATURES = {
     "ptk_search64_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p]),
     "ptk_search64_count_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_knn_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "ptk_search64_knn_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
+    "ptk_search64_count_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
+    "ptk_search64_count_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_radius": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_double, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "ptk_search64_box": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -450,6 +460,13 @@ def _adopt(lib, ptr: c_void_p, count: int, dtype) -> np.ndarray:
 
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
+
+
+def _is_scalar_radius(radius) -> bool:
+    """One radius for the batch (a number, a 0-d array or tensor) rather than an array of one per query."""
+    if _is_torch(radius):
+        return radius.dim() == 0
+    return np.ndim(radius) == 0
 
 
 class DArray:
@@ -842,9 +859,15 @@ class KdTree:
         ``(index -1, distance radius)`` (``ptk_search_knn_within`` / ``ptk_search64_knn_within``).  Exact;
         float32 and float64 trees.  Layouts as :meth:`search_knn`: host arrays give numpy rows (``(k, nq)`` for
         column-major queries), a torch CUDA tensor gives a :class:`DeviceNeighbors`.
+
+        ``radius`` may also be a 1-D array of ``nq`` radii, one per query row (``ptk_search_knn_within_radii``): row i
+        is then the row the scalar call gives with ``radius[i]``.  Host queries take any array-like (converted to the
+        tree's dtype; a NaN or negative entry raises); torch CUDA queries take a contiguous CUDA tensor of the tree's
+        dtype on the same device (not inspected: a row whose radius is NaN or negative is all padding).
         """
         k = int(k)
-        r = self._real(radius)
+        radii = None if _is_scalar_radius(radius) else radius
+        r = self._real(radius) if radii is None else None
         NB = self._neighbor
         if _is_torch(pts):
             import torch
@@ -860,11 +883,19 @@ class KdTree:
                 out = (torch.zeros if self._f64 else torch.empty)((nq, k, 2), dtype=traw, device=pts.device)
             if out.dtype != traw or tuple(out.shape) != (nq, k, 2) or not out.is_contiguous():
                 raise ValueError(f"nns must be a contiguous {traw} (nq, k, 2) tensor")
+            if radii is not None:
+                radii = self._device_radii(radii, pts, nq)
             stream = torch.cuda.current_stream(pts.device).cuda_stream
+            if radii is not None:
+                _check(self._fn("ptk_search_knn_within_radii_device")(self._h, pts.data_ptr(), nq, k, radii.data_ptr(),
+                                                                     out.data_ptr(), stream))
+                return DeviceNeighbors(out)
             _check(self._fn("ptk_search_knn_within_device")(self._h, pts.data_ptr(), nq, k, r, out.data_ptr(), stream))
             return DeviceNeighbors(out)
         q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
         nq = q.shape[0]
+        if radii is not None:
+            radii = self._host_radii(radii, nq)
         shape = (nq,) if k == 1 else ((nq, k) if pts.flags.c_contiguous else (k, nq))
         if nns is None:
             nns = np.zeros(shape, dtype=NB) if self._f64 else np.empty(shape, dtype=NB)
@@ -877,9 +908,15 @@ class KdTree:
                 nns = np.zeros(shape, dtype=NB)
         # (column-major callers: row i of the search is column i of the output, as search_knn)
         rows = nns if k == 1 or pts.flags.c_contiguous else np.zeros((nq, k), dtype=NB)
-        self._served(self._fn("ptk_search_knn_within")(self._h, q.ctypes.data, nq, k, r, rows.ctypes.data),
-                     lambda lib: lib.ptk_host_search_knn_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq, k,
-                                                                np.float32(radius), rows.ctypes.data))
+        if radii is not None:
+            self._served(self._fn("ptk_search_knn_within_radii")(self._h, q.ctypes.data, nq, k, radii.ctypes.data,
+                                                                rows.ctypes.data),
+                         lambda lib: lib.ptk_host_search_knn_within_radii(self._h, self._pts.ctypes.data, q.ctypes.data,
+                                                                          nq, k, radii.ctypes.data, rows.ctypes.data))
+        else:
+            self._served(self._fn("ptk_search_knn_within")(self._h, q.ctypes.data, nq, k, r, rows.ctypes.data),
+                         lambda lib: lib.ptk_host_search_knn_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq, k,
+                                                                    np.float32(radius), rows.ctypes.data))
         if rows is not nns:
             nns.reshape(-1)[:] = rows.reshape(-1)
         return nns
@@ -892,8 +929,13 @@ class KdTree:
         ``ptk_search64_count_within``).  Exact; the rows are never built.  Host arrays (row- or column-major, the
         tree's dtype) give an ``int64[nq]`` array; a torch CUDA tensor gives an ``int64`` tensor on its device, enqueued
         on the current stream.
+
+        ``radius`` may also be a 1-D array of ``nq`` radii, one per query row (``ptk_search_count_within_radii``), as for
+        :meth:`search_knn_within`; ``max_count`` stays one value.  The device serves that form for trees of up to three
+        dimensions and the four non-topological metrics; the rest is refused (``allow_host_loop`` serves float32 trees).
         """
-        r = self._real(radius)
+        radii = None if _is_scalar_radius(radius) else radius
+        r = self._real(radius) if radii is None else None
         max_count = int(max_count)
         if max_count < 0:
             raise ValueError("max_count must be >= 0")
@@ -906,17 +948,64 @@ class KdTree:
                 raise ValueError("queries must be a contiguous CUDA tensor")
             nq = pts.shape[0]
             out = torch.empty((nq,), dtype=torch.int64, device=pts.device)
+            if radii is not None:
+                radii = self._device_radii(radii, pts, nq)
             stream = torch.cuda.current_stream(pts.device).cuda_stream
+            if radii is not None:
+                _check(self._fn("ptk_search_count_within_radii_device")(self._h, pts.data_ptr(), nq, radii.data_ptr(),
+                                                                       max_count, out.data_ptr(), stream))
+                return out
             _check(self._fn("ptk_search_count_within_device")(self._h, pts.data_ptr(), nq, r, max_count, out.data_ptr(),
                                                              stream))
             return out
         q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
         nq = q.shape[0]
         counts = np.zeros((nq,), dtype=np.int64)
+        if radii is not None:
+            radii = self._host_radii(radii, nq)
+            self._served(self._fn("ptk_search_count_within_radii")(self._h, q.ctypes.data, nq, radii.ctypes.data, max_count,
+                                                                  counts.ctypes.data),
+                         lambda lib: lib.ptk_host_search_count_within_radii(self._h, self._pts.ctypes.data, q.ctypes.data,
+                                                                            nq, radii.ctypes.data, max_count,
+                                                                            counts.ctypes.data))
+            return counts
         self._served(self._fn("ptk_search_count_within")(self._h, q.ctypes.data, nq, r, max_count, counts.ctypes.data),
                      lambda lib: lib.ptk_host_search_count_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq,
                                                                   np.float32(radius), max_count, counts.ctypes.data))
         return counts
+
+    def _host_radii(self, radii, nq: int):
+        """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""
+        if _is_torch(radii):
+            if radii.is_cuda:
+                raise ValueError("radius: host queries take host radii, not a CUDA tensor")
+            radii = radii.numpy()
+        try:
+            radii = np.ascontiguousarray(radii, dtype=self._dtype)
+        except (TypeError, ValueError) as ex:
+            raise ValueError(f"radius: not an array of numbers ({ex})") from None
+        if radii.ndim != 1:
+            raise ValueError(f"radius must be a scalar or a 1-D array of one radius per query, not {radii.ndim}-D")
+        if radii.shape[0] != nq:
+            raise ValueError(f"radius holds {radii.shape[0]} entries for {nq} queries")
+        return radii
+
+    def _device_radii(self, radii, pts, nq: int):
+        """The per-row radii of a torch CUDA batch: a contiguous 1-D CUDA tensor of the tree's dtype on the queries'
+        device, taken as it is (no copy, no look at the values)."""
+        if not _is_torch(radii):
+            raise ValueError("radius: CUDA queries take a scalar or a CUDA tensor of one radius per query")
+        if not radii.is_cuda or radii.device != pts.device:
+            raise ValueError(f"radius must be on the queries' device ({pts.device}), not on {radii.device}")
+        if radii.dtype != pts.dtype:
+            raise ValueError(f"radius must be a {self._dtype.name} tensor, not {radii.dtype}")
+        if radii.dim() != 1:
+            raise ValueError(f"radius must be a scalar or a 1-D tensor of one radius per query, not {radii.dim()}-D")
+        if radii.shape[0] != nq:
+            raise ValueError(f"radius holds {radii.shape[0]} entries for {nq} queries")
+        if not radii.is_contiguous():
+            raise ValueError("radius must be a contiguous tensor")
+        return radii
 
     def _served(self, status: int, host_loop) -> None:
         """``_check``: every failure raises.  Only after ``allow_host_loop(True)`` is a search the DEVICE refuses for a

@@ -1012,6 +1012,11 @@ int radius_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, 
 }
 using ptkf::knn_deep;
 using ptkf::knn_within_deep;
+int knn_within_radii_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k,
+                          const float* d_radii, ptk::Neighbor* d_out, hipStream_t s) {
+  return ptkf::knn_nd_within_radii_deep(t, dev, d_q, n, k, d_radii, d_out, s);
+}
+using ptkf::knn_within_radii_deep;
 using ptkf::radius_deep;
 
 // Very large batches go through in pieces of at most 2^25 queries: the scratch of a piece stays
@@ -1789,8 +1794,7 @@ static int search_knn_host(const ptk_tree* t, const float* q, uint64_t nq, uint3
 // the rows are stored -- where that argument does not hold: metrics whose box distance is no lower bound of the point
 // distances (metric_lpinf / metric_lninf), a radius that is subnormal or whose margin overflows.
 static float within_seed(const ptk_tree* t, float radius) {
-  const int m = t->metric.load();
-  if (m == PTK_METRIC_LPINF || m == PTK_METRIC_LNINF) return 3.402823466e+38f;
+  if (ptkf::unseeded_metric(t->metric.load())) return 3.402823466e+38f;
   if (radius != 0.0f && !std::isnormal(radius)) return 3.402823466e+38f;
   const float seed = radius * (1.0f + 0x1p-10f);
   return std::isfinite(seed) ? seed : 3.402823466e+38f;
@@ -1826,24 +1830,63 @@ int ptk_search_knn_within_device(const ptk_tree* t, const float* d_q, uint64_t n
   });
 }
 
+// search_knn_within_radii (ptk.h): knn_within_piece_device with a device array of one radius per row of the piece.  The
+// lanes derive their seeds (within_seed() on the device: within_seed_row, ptk_kernels.hpp); the batch order is the scalar
+// form's.
+static int knn_within_radii_piece_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, const float* d_radii,
+                                         ptk::Neighbor* d_out, hipStream_t s) {
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  Scratch scratch(t, s, /*per_stream=*/true);
+  if (deep_tree(t)) {  // unseeded, each row masked at its own radius
+    return deep_pieces(t, nq, s, scratch, 0, nq, [&](const auto& dev, uint64_t lo, uint64_t n) {
+      return knn_within_radii_deep(t, dev, d_q + lo * t->dim, n, k, d_radii + lo, d_out + lo * k, s);
+    });
+  }
+  uint32_t* perm = nullptr;
+  const int rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, t->dim <= 3 ? ptk::kCellsEmptyFirst : 0u);
+  if (rc != PTK_OK) return rc;
+  if (t->dim > 3) return ptkf::knn_nd_within_radii(t, d_q, perm, nq, k, d_radii, d_out, s);
+  return ptkf::knn_within_radii(t, d_q, perm, nq, k, d_radii, d_out, s);
+}
+
+int ptk_search_knn_within_radii_device(const ptk_tree* t, const float* d_q, uint64_t nq, uint32_t k, const float* d_radii,
+                                       ptk_neighbor* d_out, void* stream) {
+  const int rc = check_knn_within_radii(t, d_q, nq, k, d_radii, d_out, /*host_values=*/false);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return in_batch_pieces(nq, [&](uint64_t first, uint64_t n) {
+    return knn_within_radii_piece_device(t, d_q + first * t->dim, n, k, d_radii + first,
+                                         reinterpret_cast<ptk::Neighbor*>(d_out) + first * k,
+                                         static_cast<hipStream_t>(stream));
+  });
+}
+
 }  // extern "C"
 
 namespace {
 
 // The host-buffer form of a search whose rows have one size: the batch goes up, is searched on one stream of the
 // handle and comes down, under the handle's I/O lock.  `search(d_q, d_out, stream)` is the _device form.
+// The _radii forms pass `radii` (nq host values): they go up behind the queries in the same input block, and *d_radii is
+// where `search` finds them.
 template <class Search>
-int host_round_trip(const ptk_tree* t, const float* q, uint64_t nq, void* out, size_t out_bytes, Search&& search) {
+int host_round_trip(const ptk_tree* t, const float* q, uint64_t nq, void* out, size_t out_bytes, Search&& search,
+                    const float* radii = nullptr, const float** d_radii = nullptr) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   const size_t in_bytes = (size_t)nq * t->dim * sizeof(float);
+  const size_t radii_bytes = radii != nullptr ? (size_t)nq * sizeof(float) : 0;
   HostIo& io = t->io;
   std::lock_guard<std::mutex> lock(io.mutex);
   if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int rc = grow_device_block(&io.d_in, &io.in_capacity, in_bytes);
+  int rc = grow_device_block(&io.d_in, &io.in_capacity, in_bytes + radii_bytes);
   if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
   if (rc != PTK_OK) return rc;
   PTK_HIP(hipMemcpyAsync(io.d_in, q, in_bytes, hipMemcpyHostToDevice, io.search[0]));
+  if (radii != nullptr) {
+    PTK_HIP(hipMemcpyAsync(io.d_in + in_bytes, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
+    *d_radii = reinterpret_cast<const float*>(io.d_in + in_bytes);
+  }
   rc = search(reinterpret_cast<const float*>(io.d_in), io.d_out, io.search[0]);
   if (rc != PTK_OK) {
     (void)hipStreamSynchronize(io.search[0]);
@@ -1864,6 +1907,19 @@ int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32
   return host_round_trip(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor), [&](const float* d_q, char* d_out, hipStream_t s) {
     return ptk_search_knn_within_device(t, d_q, nq, k, radius, reinterpret_cast<ptk_neighbor*>(d_out), s);
   });
+}
+
+int ptk_search_knn_within_radii(const ptk_tree* t, const float* q, uint64_t nq, uint32_t k, const float* radii,
+                                ptk_neighbor* out) {
+  const int rc = check_knn_within_radii(t, q, nq, k, radii, out, /*host_values=*/true);
+  if (rc != PTK_OK || nq == 0) return rc;
+  const float* d_radii = nullptr;
+  return host_round_trip(
+      t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor),
+      [&](const float* d_q, char* d_out, hipStream_t s) {
+        return ptk_search_knn_within_radii_device(t, d_q, nq, k, d_radii, reinterpret_cast<ptk_neighbor*>(d_out), s);
+      },
+      radii, &d_radii);
 }
 
 // ---- neighbour counts within a radius ---------------------------------------
@@ -1928,6 +1984,38 @@ int ptk_search_count_within(const ptk_tree* t, const float* q, uint64_t nq, floa
   return host_round_trip(t, q, nq, counts, (size_t)nq * sizeof(uint64_t), [&](const float* d_q, char* d_out, hipStream_t s) {
     return ptk_search_count_within_device(t, d_q, nq, radius, max_count, reinterpret_cast<uint64_t*>(d_out), s);
   });
+}
+
+// count_within_radii (ptk.h): the side-table kernel -- the table the scalar call builds and uses, whichever comes first --
+// with a radius per row; every handle the scalar call sends through the radius search's count pass is refused
+// (check_count_within_radii).  The batch order is the scalar call's.
+int ptk_search_count_within_radii_device(const ptk_tree* t, const float* d_q, uint64_t nq, const float* d_radii,
+                                         uint64_t max_count, uint64_t* d_counts, void* stream) {
+  int rc = check_count_within_radii(t, d_q, nq, d_radii, d_counts, /*host_values=*/false);
+  if (rc != PTK_OK || nq == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = count_table_of(t, s);
+  if (rc != PTK_OK) return rc;
+  Scratch scratch(t, s, /*per_stream=*/true);
+  uint32_t* perm = nullptr;
+  rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, ptk::kCellsDenseFirst);
+  if (rc != PTK_OK) return rc;
+  return ptkf::count_within_radii(t, d_q, perm, nq, d_radii, max_count, knob_int("count_shortcut", 1) != 0, d_counts, s);
+}
+
+int ptk_search_count_within_radii(const ptk_tree* t, const float* q, uint64_t nq, const float* radii, uint64_t max_count,
+                                  uint64_t* counts) {
+  const int rc = check_count_within_radii(t, q, nq, radii, counts, /*host_values=*/true);
+  if (rc != PTK_OK || nq == 0) return rc;
+  const float* d_radii = nullptr;
+  return host_round_trip(
+      t, q, nq, counts, (size_t)nq * sizeof(uint64_t),
+      [&](const float* d_q, char* d_out, hipStream_t s) {
+        return ptk_search_count_within_radii_device(t, d_q, nq, d_radii, max_count, reinterpret_cast<uint64_t*>(d_out), s);
+      },
+      radii, &d_radii);
 }
 
 // ---- radius -------------------------------------------------------------------------------

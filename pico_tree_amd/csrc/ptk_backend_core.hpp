@@ -645,6 +645,50 @@ inline int check_count_within(const Tree* t, const void* q, uint64_t nq, double 
   return PTK_OK;
 }
 
+// The _radii forms (ptk.h): the scalar form's checks with an array of nq radii in place of the one.  `host_values`:
+// the array is host memory (the host-buffer forms and the host loops) and is scanned -- the first NaN or negative entry
+// is refused by its row; a _device form only enqueues and cannot look (ptk.h says what such a row gives).
+template <class Real>
+inline int check_radii(const Real* radii, uint64_t nq, bool host_values) {
+  if (radii == nullptr) return fail(PTK_ERR_INVALID, "null radii buffer");
+  if (!host_values) return PTK_OK;
+  for (uint64_t i = 0; i < nq; ++i) {
+    if (!(radii[i] >= Real(0)))
+      return fail(PTK_ERR_INVALID, "radii[%llu] must be >= 0 (and not NaN)", (unsigned long long)i);
+  }
+  return PTK_OK;
+}
+template <class Tree, class Real>
+inline int check_knn_within_radii(const Tree* t, const void* q, uint64_t nq, uint32_t k, const Real* radii, const void* out,
+                                  bool host_values) {
+  int rc = check_search(t, q, nq);
+  if (rc == PTK_OK) rc = check_k(k);
+  if (rc != PTK_OK || nq == 0) return rc;
+  rc = check_radii(radii, nq, host_values);
+  if (rc != PTK_OK) return rc;
+  if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
+  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  return PTK_OK;
+}
+// The device serves count_within_radii with the side-table kernels only (dim <= 3, the four non-topological metrics, not
+// the deep stack class): the other handles count through the radius search's count pass, whose kernels take one radius.
+inline bool deep_stack_class(const ptk_tree* t) { return deep_tree(t); }
+inline bool deep_stack_class(const ptk_tree64*) { return false; }  // (float64 stacks live in HBM at any depth)
+template <class Tree, class Real>
+inline int check_count_within_radii(const Tree* t, const void* q, uint64_t nq, const Real* radii, const void* counts,
+                                    bool host_values) {
+  int rc = check_search(t, q, nq);
+  if (rc != PTK_OK || nq == 0) return rc;
+  rc = check_radii(radii, nq, host_values);
+  if (rc != PTK_OK) return rc;
+  if (counts == nullptr) return fail(PTK_ERR_INVALID, "null counts buffer");
+  if (t->dim > 3) return fail(PTK_ERR_UNSUPPORTED, "count_within_radii: dim > 3 runs on the host loop only");
+  if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "count_within_radii: topological metrics run on the host loop only");
+  if (deep_stack_class(t))
+    return fail(PTK_ERR_UNSUPPORTED, "count_within_radii: tree depth %u runs on the host loop only", t->max_depth);
+  return PTK_OK;
+}
+
 inline float inv_ratio(float e) { return 1.0f / e; }
 
 

@@ -223,16 +223,22 @@ struct IoBuffer {
 // are ptk_neighbor64 records, whose padding bytes no kernel writes: the block is cleared first.
 template <class Search>
 int host_round_trip64(const ptk_tree64* t, const double* q, uint64_t nq, void* out, size_t out_bytes, bool records,
-                      Search&& search) {
+                      Search&& search, const double* radii = nullptr, const double** d_radii = nullptr) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   std::lock_guard<std::mutex> io_lock(t->io_mutex);
   IoBuffer bq, bo;
   const size_t qbytes = (size_t)nq * t->dim * sizeof(double);
-  hipError_t he = bq.get(t, 0, qbytes);
+  // (the _radii forms: the nq radii travel behind the queries in the same block)
+  const size_t rbytes = radii != nullptr ? (size_t)nq * sizeof(double) : 0;
+  hipError_t he = bq.get(t, 0, qbytes + rbytes);
   if (he == hipSuccess) he = bo.get(t, 1, out_bytes);
   if (he == hipSuccess && records) he = hipMemset(bo.p, 0, out_bytes ? out_bytes : 16);
   if (he == hipSuccess) he = hipMemcpy(bq.p, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess && radii != nullptr) {
+    he = hipMemcpy(bq.p + qbytes, radii, rbytes, hipMemcpyHostToDevice);
+    *d_radii = reinterpret_cast<const double*>(bq.p + qbytes);
+  }
   int rc = PTK_OK;
   if (he == hipSuccess) {
     rc = search(reinterpret_cast<const double*>(bq.p), bo.p);
@@ -409,44 +415,59 @@ int launch_knn64(const ptk_tree64* t, const double* d_q, const uint32_t* perm, u
   return PTK_OK;
 }
 
-// search_knn_within: launch_knn64's kernels in their bounded form; never capped.
-template <class M>
-int launch_knn64_within(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq, uint32_t k,
-                        double seed, double radius, ptk::Neighbor64* d_out, hipStream_t s, Stack64Lease& lease) {
+// search_knn_within: launch_knn64's kernels in their bounded form; never capped.  `r`: ptkf::WithinOne
+// (the scalar call's kernels) or ptkf::WithinRows (their per-row forms) -- one dispatch for both.
+template <class M, class R>
+int launch_knn64_within(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const R& r,
+                        ptk::Neighbor64* d_out, hipStream_t s, Stack64Lease& lease) {
   if constexpr (M::kTopo) {
     return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
   } else {
+  constexpr bool kRows = ptkf::within_rows<R>::value;
   const bool d3 = t->dim <= 3;
   const size_t smem = ptk::lds64_bytes(d3 ? 0 : 2, t->dim);
   if (smem > 160 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dim %u needs %zu bytes of LDS per wavefront (> 160 KiB)", t->dim, smem);
   int rc = PTK_OK;
   // (register list for k <= 64 with dim <= 3, k <= 32 otherwise -- the VGPR budget of launch_knn64)
   const int reg = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 && d3 ? 64 : 0))));
-#define PTK_LAUNCH64_WITHIN(KERNEL)                                                                                   \
+#define PTK_LAUNCH64_ONE(KERNEL, A, B)                                                                                \
   do {                                                                                                                \
     rc = allow_lds(KERNEL, smem);                                                                                     \
     if (rc != PTK_OK) return rc;                                                                                      \
     for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {                                                               \
       const uint64_t n = std::min(lease.piece, nq - q0);                                                              \
       hipLaunchKernelGGL(KERNEL, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k,   \
-                         d_out, lease.stack, t->slots, seed, radius);                                                \
+                         d_out, lease.stack, t->slots, A, B);                                                        \
     }                                                                                                                 \
   } while (0)
+  // (NAME<ARGS>: the scalar call's kernel; NAME##_radii... is spelled out by the two macros below)
+#define PTK_LAUNCH64_REG_WITHIN(KK, D3)                                                                               \
+  do {                                                                                                                \
+    if constexpr (kRows) PTK_LAUNCH64_ONE((ptk::knn64_reg_within_radii_kernel<M, KK, D3>), r.radii, r.unseeded);      \
+    else PTK_LAUNCH64_ONE((ptk::knn64_reg_within_kernel<M, KK, D3>), r.seed, r.radius);                               \
+  } while (0)
+#define PTK_LAUNCH64_ROW_WITHIN(D3)                                                                                   \
+  do {                                                                                                                \
+    if constexpr (kRows) PTK_LAUNCH64_ONE((ptk::knn64_within_radii_kernel<M, D3>), r.radii, r.unseeded);              \
+    else PTK_LAUNCH64_ONE((ptk::knn64_within_kernel<M, D3>), r.seed, r.radius);                                       \
+  } while (0)
   if (d3) {
-    if (reg == 4) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 4, true>));
-    else if (reg == 8) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 8, true>));
-    else if (reg == 16) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 16, true>));
-    else if (reg == 32) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 32, true>));
-    else if (reg == 64) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 64, true>));
-    else PTK_LAUNCH64_WITHIN((ptk::knn64_within_kernel<M, true>));
+    if (reg == 4) PTK_LAUNCH64_REG_WITHIN(4, true);
+    else if (reg == 8) PTK_LAUNCH64_REG_WITHIN(8, true);
+    else if (reg == 16) PTK_LAUNCH64_REG_WITHIN(16, true);
+    else if (reg == 32) PTK_LAUNCH64_REG_WITHIN(32, true);
+    else if (reg == 64) PTK_LAUNCH64_REG_WITHIN(64, true);
+    else PTK_LAUNCH64_ROW_WITHIN(true);
   } else {
-    if (reg == 4) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 4, false>));
-    else if (reg == 8) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 8, false>));
-    else if (reg == 16) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 16, false>));
-    else if (reg == 32) PTK_LAUNCH64_WITHIN((ptk::knn64_reg_within_kernel<M, 32, false>));
-    else PTK_LAUNCH64_WITHIN((ptk::knn64_within_kernel<M, false>));
+    if (reg == 4) PTK_LAUNCH64_REG_WITHIN(4, false);
+    else if (reg == 8) PTK_LAUNCH64_REG_WITHIN(8, false);
+    else if (reg == 16) PTK_LAUNCH64_REG_WITHIN(16, false);
+    else if (reg == 32) PTK_LAUNCH64_REG_WITHIN(32, false);
+    else PTK_LAUNCH64_ROW_WITHIN(false);
   }
-#undef PTK_LAUNCH64_WITHIN
+#undef PTK_LAUNCH64_ROW_WITHIN
+#undef PTK_LAUNCH64_REG_WITHIN
+#undef PTK_LAUNCH64_ONE
   PTK_HIP(hipGetLastError());
   return PTK_OK;
   }
@@ -981,15 +1002,15 @@ int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint6
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   double seed = radius * (1.0 + 0x1p-10);
-  if (m == PTK_METRIC_LPINF || m == PTK_METRIC_LNINF || t->max_depth > 1024u || (radius != 0.0 && !std::isnormal(radius)) ||
+  if (ptkf::unseeded_metric(m) || t->max_depth > 1024u || (radius != 0.0 && !std::isnormal(radius)) ||
       !std::isfinite(seed))
     seed = 1.7976931348623157e+308;
   Stack64Lease lease(t, s);
   const uint32_t* perm = nullptr;
   rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
   if (rc != PTK_OK) return rc;
-  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, seed, radius, reinterpret_cast<ptk::Neighbor64*>(d_out),
-                                                s, lease));
+  const ptkf::WithinOne<double> r{seed, radius};
+  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, r, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease));
   return rc;
 }
 
@@ -1002,6 +1023,39 @@ int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, u
                              return ptk_search64_knn_within_device(t, d_q, nq, k, radius,
                                                                    reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
                            });
+}
+
+// search_knn_within_radii (ptk.h): the same launch with the per-row kernels; each lane derives its seed
+// from its own radius, unseeded for the whole call where the scalar form is for every radius.
+int ptk_search64_knn_within_radii_device(const ptk_tree64* t, const double* d_q, uint64_t nq, uint32_t k,
+                                         const double* d_radii, ptk_neighbor64* d_out, void* stream) {
+  int rc = check_knn_within_radii(t, d_q, nq, k, d_radii, d_out, /*host_values=*/false);
+  if (rc != PTK_OK || nq == 0) return rc;
+  const int m = t->metric.load();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const bool unseeded = ptkf::unseeded_metric(m) || t->max_depth > 1024u;
+  Stack64Lease lease(t, s);
+  const uint32_t* perm = nullptr;
+  rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
+  if (rc != PTK_OK) return rc;
+  const ptkf::WithinRows<double> r{d_radii, unseeded ? 1u : 0u};
+  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, r, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease));
+  return rc;
+}
+
+int ptk_search64_knn_within_radii(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, const double* radii,
+                                  ptk_neighbor64* out) {
+  const int rc = check_knn_within_radii(t, q, nq, k, radii, out, /*host_values=*/true);
+  if (rc != PTK_OK || nq == 0) return rc;
+  const double* d_radii = nullptr;
+  return host_round_trip64(
+      t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
+      [&](const double* d_q, char* d_out) {
+        return ptk_search64_knn_within_radii_device(t, d_q, nq, k, d_radii, reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
+      },
+      radii, &d_radii);
 }
 
 // count_within (ptk.h): dim <= 3 and the four non-topological metrics take count64_within_kernel (the
@@ -1059,6 +1113,43 @@ int ptk_search64_count_within(const ptk_tree64* t, const double* q, uint64_t nq,
                              return ptk_search64_count_within_device(t, d_q, nq, radius, max_count,
                                                                      reinterpret_cast<uint64_t*>(d_out), nullptr);
                            });
+}
+
+// count_within_radii (ptk.h): the side-table kernel with a radius per row; the handles the scalar call serves through
+// the radius search's count pass are refused (check_count_within_radii).
+int ptk_search64_count_within_radii_device(const ptk_tree64* t, const double* d_q, uint64_t nq, const double* d_radii,
+                                           uint64_t max_count, uint64_t* d_counts, void* stream) {
+  int rc = check_count_within_radii(t, d_q, nq, d_radii, d_counts, /*host_values=*/false);
+  if (rc != PTK_OK || nq == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = count_table64_of(t, s);
+  if (rc != PTK_OK) return rc;
+  Stack64Lease lease(t, s);
+  const uint32_t* perm = nullptr;
+  rc = order_batch64(t, d_q, nq, s, lease, 0, &perm);
+  if (rc != PTK_OK) return rc;
+  const bool shortcut = knob_int("count_shortcut", 1) != 0;
+  for (uint64_t q0 = 0; q0 < nq && rc == PTK_OK; q0 += lease.piece)
+    rc = ptkf::count64_within_radii(t->dev, t->metric.load(), static_cast<const ptk::CountBox64*>(t->d_count_table), d_q, perm,
+                                    q0, std::min(lease.piece, nq - q0), d_radii, max_count, shortcut, d_counts, lease.stack,
+                                    t->slots, s);
+  return rc;
+}
+
+int ptk_search64_count_within_radii(const ptk_tree64* t, const double* q, uint64_t nq, const double* radii,
+                                    uint64_t max_count, uint64_t* counts) {
+  const int rc = check_count_within_radii(t, q, nq, radii, counts, /*host_values=*/true);
+  if (rc != PTK_OK || nq == 0) return rc;
+  const double* d_radii = nullptr;
+  return host_round_trip64(
+      t, q, nq, counts, (size_t)nq * sizeof(uint64_t), /*records=*/false,
+      [&](const double* d_q, char* d_out) {
+        return ptk_search64_count_within_radii_device(t, d_q, nq, d_radii, max_count, reinterpret_cast<uint64_t*>(d_out),
+                                                      nullptr);
+      },
+      radii, &d_radii);
 }
 
 int ptk_tree64_debug_knn_coop_counts(const ptk_tree64* t, uint32_t counts[7]) {

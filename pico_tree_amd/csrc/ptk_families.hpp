@@ -12,6 +12,26 @@ struct Rec64;
 }  // namespace ptk
 
 namespace ptkf {
+// What a bounded launch takes its radius from: the scalar entry points' {seed, radius}, or the per-row entry points'
+// device array of radii (`unseeded`: the lanes start their lists at FLT_MAX / DBL_MAX whatever the row's radius is).  The
+// launch wrappers are written once over either, so the dispatch of the two forms cannot drift apart.
+template <class Real>
+struct WithinOne {
+  Real seed, radius;
+};
+template <class Real>
+struct WithinRows {
+  const Real* radii;
+  uint32_t unseeded;
+};
+// Does a bounded k-list of this metric start unseeded whatever the radius is?  metric_lpinf / metric_lninf: their box
+// distance is no lower bound of the point distances.  The one statement of it, for the scalar seed
+// (within_seed, ptk_backend.hip; ptk_search64_knn_within_device) and for the per-row launches alike.
+inline bool unseeded_metric(int metric) { return metric == PTK_METRIC_LPINF || metric == PTK_METRIC_LNINF; }
+template <class R>
+struct within_rows : std::false_type {};
+template <class Real>
+struct within_rows<WithinRows<Real>> : std::true_type {};
 // ptk_backend.hip: the batch order (the library's radix sort of 32-bit keys; rocprim is compiled into that unit only)
 int morton_bits(uint64_t nq);
 size_t sort_tmp_bytes(uint64_t nq, int bits);
@@ -31,6 +51,11 @@ int knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64
                ptk::Neighbor* d_out, hipStream_t s);
 int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
                     ptk::Neighbor* d_out, hipStream_t s);
+// search_knn_within_radii (ptk.h): row i bounded by d_radii[i], i the row in the caller's order
+int knn_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const float* d_radii,
+                     ptk::Neighbor* d_out, hipStream_t s);
+int knn_within_radii_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k,
+                          const float* d_radii, ptk::Neighbor* d_out, hipStream_t s);
 void warm_knn();
 // ptk_family_radius.hip: 3-D float32 trees
 int radius_traverse(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e, bool fill,
@@ -67,6 +92,10 @@ int knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uin
                   float radius, ptk::Neighbor* d_out, hipStream_t s);
 int knn_nd_within_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
                        ptk::Neighbor* d_out, hipStream_t s);
+int knn_nd_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k,
+                        const float* d_radii, ptk::Neighbor* d_out, hipStream_t s);
+int knn_nd_within_radii_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k,
+                             const float* d_radii, ptk::Neighbor* d_out, hipStream_t s);
 void warm_nd();
 // ptk_family_topo.hip: metric_so2 / metric_se2_squared
 int knn_topo(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float e,
@@ -79,6 +108,8 @@ constexpr size_t kCountBoxBytes = 32;
 int count_table(const ptk_tree* t, void** d_table, hipStream_t s);
 int count_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, uint64_t max_count,
                  bool shortcut, uint64_t* d_counts, hipStream_t s);
+int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                        uint64_t max_count, bool shortcut, uint64_t* d_counts, hipStream_t s);
 int clamp_counts(uint64_t* d_counts, uint64_t n, uint64_t max_count, hipStream_t s);
 // ... and of float64 trees with dim <= 3 (ptk_kernels_count64.hpp): kCountBox64Bytes per branch
 constexpr size_t kCountBox64Bytes = 64;
@@ -86,6 +117,9 @@ int count_table64(const ptk::DevTree64& dev, uint64_t n_branches, void** d_table
 int count64_within(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, const double* d_q,
                    const uint32_t* perm, uint64_t q0, uint64_t n, double radius, uint64_t max_count, bool shortcut,
                    uint64_t* d_counts, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
+int count64_within_radii(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, const double* d_q,
+                         const uint32_t* perm, uint64_t q0, uint64_t n, const double* d_radii, uint64_t max_count,
+                         bool shortcut, uint64_t* d_counts, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
 void warm_count();
 // ptk_family_f64.hip
 void warm_f64();

@@ -24,6 +24,20 @@ int launch_count_within(const ptk_tree* t, const float* d_q, const uint32_t* per
   return PTK_OK;
 }
 
+// count_within_radii: launch_count_within with the per-row kernel.
+template <int S, int OVF, int LEAFB, class M>
+int launch_count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                              uint64_t max_count, bool shortcut, uint64_t* d_counts, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((nq + 63) / 64);
+  Timer timer(t, s);
+  hipLaunchKernelGGL((ptk::count_within_radii_kernel<S, OVF, 64, LEAFB, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                     t->dev, static_cast<const ptk::CountBox*>(t->d_count_table), d_q, t->dim, perm, nq, d_radii, max_count,
+                     shortcut ? 1u : 0u, d_counts, nullptr);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, nq);
+  return PTK_OK;
+}
+
 static __global__ void warm_count_kernel() {}
 
 }  // namespace
@@ -61,6 +75,14 @@ int count_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint
   int rc = PTK_OK;
   PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_within<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, radius, max_count, shortcut,
                                                                             d_counts, s))));
+  return rc;
+}
+
+int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                        uint64_t max_count, bool shortcut, uint64_t* d_counts, hipStream_t s) {
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_within_radii<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, d_radii, max_count,
+                                                                                  shortcut, d_counts, s))));
   return rc;
 }
 
@@ -119,6 +141,34 @@ int count64_within(const ptk::DevTree64& dev, int metric, const ptk::CountBox64*
     default:
       hipLaunchKernelGGL(ptk::count64_within_kernel<ptk::Metric64L2>, grid, block, smem, s, dev, table, d_q, perm, q0, n,
                          radius, max_count, sc, d_counts, stack, slots, nullptr);
+      break;
+  }
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+int count64_within_radii(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, const double* d_q,
+                         const uint32_t* perm, uint64_t q0, uint64_t n, const double* d_radii, uint64_t max_count,
+                         bool shortcut, uint64_t* d_counts, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+  const size_t smem = ptk::lds64_bytes(0, dev.dim);
+  const uint32_t sc = shortcut ? 1u : 0u;
+  switch (metric) {
+    case PTK_METRIC_L1:
+      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64L1>, grid, block, smem, s, dev, table, d_q, perm, q0,
+                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
+      break;
+    case PTK_METRIC_LPINF:
+      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64LInf>, grid, block, smem, s, dev, table, d_q, perm, q0,
+                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
+      break;
+    case PTK_METRIC_LNINF:
+      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64LNInf>, grid, block, smem, s, dev, table, d_q, perm,
+                         q0, n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
+      break;
+    default:
+      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64L2>, grid, block, smem, s, dev, table, d_q, perm, q0,
+                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
       break;
   }
   PTK_HIP(hipGetLastError());

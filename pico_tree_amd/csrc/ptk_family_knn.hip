@@ -152,18 +152,26 @@ int launch_knn_reg(const ptk_tree* t, const float* d_q, const uint32_t* perm, ui
 
 // search_knn_within: the register list for k <= 64 -- whatever k is against n_points: an unfilled slot
 // is the pad --, the list in LDS or in the row beyond; never capped (the radius bounds every query's search).
-template <int OVF, class M>
-int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
-                      float radius, ptk::Neighbor* d_out, hipStream_t s) {
+// `r`: ptkf::WithinOne (the scalar call's kernels) or ptkf::WithinRows (their per-row forms) -- one dispatch for both.
+template <int OVF, class M, class R>
+int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const R& r,
+                      ptk::Neighbor* d_out, hipStream_t s) {
   constexpr int BLOCK = 64;
+  constexpr bool kRows = ptkf::within_rows<R>::value;
   const uint32_t blocks = (uint32_t)((nq + BLOCK - 1) / BLOCK);
   Timer timer(t, s);
   if (k <= 64) {
     constexpr int S = kGenRing;
     const size_t smem = (size_t)S * BLOCK * 8;
-#define PTK_LAUNCH_REG_WITHIN(KK)                                                                                     \
-  hipLaunchKernelGGL((ptk::knn_reg_within_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, s, \
-                     t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius)
+#define PTK_LAUNCH_REG_WITHIN(KK)                                                                                       \
+  do {                                                                                                                  \
+    if constexpr (kRows)                                                                                                \
+      hipLaunchKernelGGL((ptk::knn_reg_within_radii_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK),  \
+                         smem, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.radii, r.unseeded);                        \
+    else                                                                                                                \
+      hipLaunchKernelGGL((ptk::knn_reg_within_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, \
+                         s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.seed, r.radius);                                 \
+  } while (0)
     if (k <= 4) PTK_LAUNCH_REG_WITHIN(4);
     else if (k <= 8) PTK_LAUNCH_REG_WITHIN(8);
     else if (k <= 16) PTK_LAUNCH_REG_WITHIN(16);
@@ -174,13 +182,24 @@ int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm,
     constexpr int S = 16;
     const size_t stack_bytes = (size_t)S * BLOCK * 8, list_bytes = (size_t)k * BLOCK * 8;
     if (stack_bytes + list_bytes <= (size_t)48 * 1024) {
-      const int lds_rc = allow_lds(ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>, stack_bytes + list_bytes);
-      if (lds_rc != PTK_OK) return lds_rc;
-      hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>), dim3(blocks), dim3(BLOCK),
-                         stack_bytes + list_bytes, s, t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius);
+      if constexpr (kRows) {
+        const int lds_rc = allow_lds(ptk::knn_within_radii_kernel<S, OVF, BLOCK, 4, true, M>, stack_bytes + list_bytes);
+        if (lds_rc != PTK_OK) return lds_rc;
+        hipLaunchKernelGGL((ptk::knn_within_radii_kernel<S, OVF, BLOCK, 4, true, M>), dim3(blocks), dim3(BLOCK),
+                           stack_bytes + list_bytes, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.radii, r.unseeded);
+      } else {
+        const int lds_rc = allow_lds(ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>, stack_bytes + list_bytes);
+        if (lds_rc != PTK_OK) return lds_rc;
+        hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, true, M>), dim3(blocks), dim3(BLOCK),
+                           stack_bytes + list_bytes, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.seed, r.radius);
+      }
     } else {
-      hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, false, M>), dim3(blocks), dim3(BLOCK), stack_bytes, s,
-                         t->dev, d_q, t->dim, perm, nq, k, d_out, seed, radius);
+      if constexpr (kRows)
+        hipLaunchKernelGGL((ptk::knn_within_radii_kernel<S, OVF, BLOCK, 4, false, M>), dim3(blocks), dim3(BLOCK),
+                           stack_bytes, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.radii, r.unseeded);
+      else
+        hipLaunchKernelGGL((ptk::knn_within_kernel<S, OVF, BLOCK, 4, false, M>), dim3(blocks), dim3(BLOCK), stack_bytes, s,
+                           t->dev, d_q, t->dim, perm, nq, k, d_out, r.seed, r.radius);
     }
   }
   PTK_HIP(hipGetLastError());
@@ -188,6 +207,18 @@ int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm,
   return PTK_OK;
 }
 
+// (the stack class of the ring each form is launched with: kGenRing for the register list, 16 for the list kernel)
+template <class R>
+int dispatch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const R& r,
+                        ptk::Neighbor* d_out, hipStream_t s) {
+  int rc = PTK_OK;
+  if (k <= 64) {
+    PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
+  } else {
+    PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
+  }
+  return rc;
+}
 
 static __global__ void warm_knn_kernel() {}
 
@@ -223,14 +254,12 @@ int knn_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint6
 
 int knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed, float radius,
                ptk::Neighbor* d_out, hipStream_t s) {
-  int rc = PTK_OK;
-  // (the stack class of the ring each form is launched with: kGenRing for the register list, 16 for the list kernel)
-  if (k <= 64) {
-    PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
-  } else {
-    PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
-  }
-  return rc;
+  return dispatch_knn_within(t, d_q, perm, nq, k, WithinOne<float>{seed, radius}, d_out, s);
+}
+
+int knn_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const float* d_radii,
+                     ptk::Neighbor* d_out, hipStream_t s) {
+  return dispatch_knn_within(t, d_q, perm, nq, k, WithinRows<float>{d_radii, unseeded_metric(t->metric.load()) ? 1u : 0u}, d_out, s);
 }
 
 // knn_deep for search_knn_within: unseeded, masked at `radius` when the row is stored.
@@ -240,6 +269,18 @@ int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q
   PTK_WITH_METRIC({
     hipLaunchKernelGGL((ptk::knn_within_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s,
                        dev, d_q, t->dim, nullptr, n, k, d_out, 3.402823466e+38f, radius);
+  });
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+// ... and for search_knn_within_radii: unseeded, row j of the piece masked at d_radii[j].
+int knn_within_radii_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k,
+                          const float* d_radii, ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  PTK_WITH_METRIC({
+    hipLaunchKernelGGL((ptk::knn_within_radii_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8,
+                       s, dev, d_q, t->dim, nullptr, n, k, d_out, d_radii, 1u);
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;

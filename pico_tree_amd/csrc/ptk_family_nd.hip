@@ -54,25 +54,36 @@ int launch_knn_nd(const ptk_tree* t, const float* d_q, const uint32_t* perm, uin
   return PTK_OK;
 }
 
-// search_knn_within: launch_knn_nd's kernels in their bounded form.
-template <int OVF, class M>
-int launch_knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
-                         float radius, ptk::Neighbor* d_out, hipStream_t s) {
+// search_knn_within: launch_knn_nd's kernels in their bounded form.  `r`: ptkf::WithinOne (the scalar
+// call's kernels) or ptkf::WithinRows (their per-row forms) -- one dispatch for both.
+template <int OVF, class M, class R>
+int launch_knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const R& r,
+                         ptk::Neighbor* d_out, hipStream_t s) {
   constexpr int S = 16;
+  constexpr bool kRows = ptkf::within_rows<R>::value;
   const uint32_t blocks = (uint32_t)((nq + 63) / 64);
   const size_t base = (size_t)S * 64 * 8 + (size_t)t->dim * 64 * 8;
   if (base > t->lds_per_block)
     return fail(PTK_ERR_UNSUPPORTED, "dimension %u does not fit the LDS staging of the device search", t->dim);
   Timer timer(t, s);
   int rc = PTK_OK;
-  if (k <= 64) {
-#define PTK_LAUNCH_ND_REG_WITHIN(KK)                                                                                   \
-  do {                                                                                                               \
-    rc = allow_lds(ptk::knn_nd_reg_within_kernel<KK, S, OVF, M>, base);                                              \
-    if (rc == PTK_OK)                                                                                                \
-      hipLaunchKernelGGL((ptk::knn_nd_reg_within_kernel<KK, S, OVF, M>), dim3(blocks), dim3(64), base, s, t->dev_nd,  \
-                         d_q, perm, nq, k, d_out, seed, radius);                                                     \
+  // (launches `one` with the scalar call's arguments, `rows` with the per-row call's; `smem` bytes of LDS)
+#define PTK_LAUNCH_ND_WITHIN(one, rows, smem)                                                                           \
+  do {                                                                                                                  \
+    if constexpr (kRows) {                                                                                              \
+      rc = allow_lds(rows, smem);                                                                                       \
+      if (rc == PTK_OK)                                                                                                 \
+        hipLaunchKernelGGL(rows, dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q, perm, nq, k, d_out, r.radii,          \
+                           r.unseeded);                                                                                 \
+    } else {                                                                                                            \
+      rc = allow_lds(one, smem);                                                                                        \
+      if (rc == PTK_OK)                                                                                                 \
+        hipLaunchKernelGGL(one, dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q, perm, nq, k, d_out, r.seed, r.radius); \
+    }                                                                                                                   \
   } while (0)
+  if (k <= 64) {
+#define PTK_LAUNCH_ND_REG_WITHIN(KK)                                                                                    \
+  PTK_LAUNCH_ND_WITHIN((ptk::knn_nd_reg_within_kernel<KK, S, OVF, M>), (ptk::knn_nd_reg_within_radii_kernel<KK, S, OVF, M>), base)
     if (k <= 4) PTK_LAUNCH_ND_REG_WITHIN(4);
     else if (k <= 8) PTK_LAUNCH_ND_REG_WITHIN(8);
     else if (k <= 16) PTK_LAUNCH_ND_REG_WITHIN(16);
@@ -83,18 +94,12 @@ int launch_knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* pe
     const size_t list_bytes = (size_t)k * 64 * 8;
     const bool list_lds = base + list_bytes <= 64 * 1024;
     const size_t smem = base + (list_lds ? list_bytes : 0);
-    if (list_lds) {
-      rc = allow_lds(ptk::knn_nd_within_kernel<S, OVF, true, M>, smem);
-      if (rc == PTK_OK)
-        hipLaunchKernelGGL((ptk::knn_nd_within_kernel<S, OVF, true, M>), dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q,
-                           perm, nq, k, d_out, seed, radius);
-    } else {
-      rc = allow_lds(ptk::knn_nd_within_kernel<S, OVF, false, M>, smem);
-      if (rc == PTK_OK)
-        hipLaunchKernelGGL((ptk::knn_nd_within_kernel<S, OVF, false, M>), dim3(blocks), dim3(64), smem, s, t->dev_nd, d_q,
-                           perm, nq, k, d_out, seed, radius);
-    }
+    if (list_lds)
+      PTK_LAUNCH_ND_WITHIN((ptk::knn_nd_within_kernel<S, OVF, true, M>), (ptk::knn_nd_within_radii_kernel<S, OVF, true, M>), smem);
+    else
+      PTK_LAUNCH_ND_WITHIN((ptk::knn_nd_within_kernel<S, OVF, false, M>), (ptk::knn_nd_within_radii_kernel<S, OVF, false, M>), smem);
   }
+#undef PTK_LAUNCH_ND_WITHIN
   if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
   timer.stop(0, nq);
@@ -163,7 +168,17 @@ int knn_nd(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t n
 int knn_nd_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float seed,
                   float radius, ptk::Neighbor* d_out, hipStream_t s) {
   int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_nd_within<OVF, M>(t, d_q, perm, nq, k, seed, radius, d_out, s))));
+  const WithinOne<float> r{seed, radius};
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_nd_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
+  return rc;
+}
+
+// search_knn_within_radii (ptk.h): unseeded where within_seed() (ptk_backend.hip) says so for the whole call.
+int knn_nd_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k,
+                        const float* d_radii, ptk::Neighbor* d_out, hipStream_t s) {
+  int rc = PTK_OK;
+  const WithinRows<float> r{d_radii, unseeded_metric(t->metric.load()) ? 1u : 0u};
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_nd_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
   return rc;
 }
 
@@ -180,6 +195,25 @@ int knn_nd_within_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float
     if (rc == PTK_OK)
       hipLaunchKernelGGL((ptk::knn_nd_within_kernel<16, -1, false, M>), dim3(blocks), dim3(64), smem, s, dev, d_q, nullptr,
                          n, k, d_out, 3.402823466e+38f, radius);
+  });
+  if (rc != PTK_OK) return rc;
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+// ... and for search_knn_within_radii: unseeded, row j of the piece masked at d_radii[j].
+int knn_nd_within_radii_deep(const ptk_tree* t, const ptk::DevTreeND& dev, const float* d_q, uint64_t n, uint32_t k,
+                             const float* d_radii, ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  const size_t smem = (size_t)16 * 64 * 8 + (size_t)t->dim * 64 * 8;
+  if (smem > t->lds_per_block)
+    return fail(PTK_ERR_UNSUPPORTED, "dimension %u does not fit the LDS staging of the device search", t->dim);
+  int rc = PTK_OK;
+  PTK_WITH_METRIC({
+    rc = allow_lds(ptk::knn_nd_within_radii_kernel<16, -1, false, M>, smem);
+    if (rc == PTK_OK)
+      hipLaunchKernelGGL((ptk::knn_nd_within_radii_kernel<16, -1, false, M>), dim3(blocks), dim3(64), smem, s, dev, d_q,
+                         nullptr, n, k, d_out, d_radii, 1u);
   });
   if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());

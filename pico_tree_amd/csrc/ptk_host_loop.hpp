@@ -127,6 +127,66 @@ inline bool topological_without_bounds(const ptk_tree* t, const flat_t& flat) {
   return (m == PTK_METRIC_SO2 || m == PTK_METRIC_SE2_SQUARED) && !flat.keep_outer_bounds;
 }
 
+// The results contract of search_knn_within (ptk.h) as it is written: the reference's search_knn row of min(k, n_points)
+// entries, the entries not below the radius dropped, the row padded with {-1, radius}.  `radius_of(i)`: the radius of
+// row i -- one value for the scalar entry, the caller's array for the _radii entry.
+template <class RadiusOf>
+int knn_within_rows(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint32_t k, ptk_neighbor* out,
+                    RadiusOf&& radius_of) {
+  try {
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    auto* rows = reinterpret_cast<neighbor_t*>(out);
+    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, t->n_points);
+    rows_loop(nq, [&](uint64_t i) {
+      const float radius = radius_of(i);
+      neighbor_t* b = rows + i * k;
+      std::vector<neighbor_t> full(kk);
+      internal::knn_visitor<neighbor_t*> v(full.data(), full.data() + kk);
+      search_one(t, flat, view, q + i * t->dim, v);
+      // (only what the search wrote: a row no distance is below FLT_MAX from -- NaN, +-Inf -- accepts nothing)
+      const uint32_t found = (uint32_t)(v.filled() - full.data());
+      uint32_t n = 0;
+      while (n < found && full[n].distance < radius) {
+        b[n] = full[n];
+        ++n;
+      }
+      for (; n < k; ++n) b[n] = neighbor_t{-1, radius};
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// count_within (ptk.h) as it is written: the reference's radius search of each row, counting instead of pushing.
+template <class RadiusOf>
+int count_within_rows(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint64_t max_count,
+                      uint64_t* counts, RadiusOf&& radius_of) {
+  try {
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    rows_loop(nq, [&](uint64_t i) {
+      internal::count_visitor<float> v(radius_of(i), (std::size_t)max_count);
+      search_one(t, flat, view, q + i * t->dim, v);
+      counts[i] = v.count();
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 }  // namespace ptk_host
 
 extern "C" {
@@ -169,69 +229,43 @@ int ptk_host_search_knn(const ptk_tree* t, const float* points, const float* q, 
   return PTK_OK;
 }
 
-// The results contract of search_knn_within (ptk.h) as it is written: the reference's search_knn row of min(k, n_points)
-// entries, the entries not below the radius dropped, the row padded with {-1, radius}.
 int ptk_host_search_knn_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint32_t k,
                                float radius, ptk_neighbor* out) {
   if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || out == nullptr)))
     return fail(PTK_ERR_INVALID, "null argument");
   if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
   if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  try {
-    using namespace ptk_host;
-    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
-    const flat_t& flat = *flat_holder;
-    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
-    space_t space(points, t->n_points, t->dim);
-    view_t view(space);
-    auto* rows = reinterpret_cast<neighbor_t*>(out);
-    const uint32_t kk = (uint32_t)std::min<uint64_t>(k, t->n_points);
-    rows_loop(nq, [&](uint64_t i) {
-      neighbor_t* b = rows + i * k;
-      std::vector<neighbor_t> full(kk);
-      internal::knn_visitor<neighbor_t*> v(full.data(), full.data() + kk);
-      search_one(t, flat, view, q + i * t->dim, v);
-      // (only what the search wrote: a row no distance is below FLT_MAX from -- NaN, +-Inf -- accepts nothing)
-      const uint32_t found = (uint32_t)(v.filled() - full.data());
-      uint32_t n = 0;
-      while (n < found && full[n].distance < radius) {
-        b[n] = full[n];
-        ++n;
-      }
-      for (; n < k; ++n) b[n] = neighbor_t{-1, radius};
-    });
-  } catch (const std::bad_alloc&) {
-    return fail(PTK_ERR_NOMEM, "out of host memory");
-  } catch (const std::exception& ex) {
-    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
-  }
-  return PTK_OK;
+  return ptk_host::knn_within_rows(t, points, q, nq, k, out, [radius](uint64_t) { return radius; });
 }
 
-// count_within (ptk.h) as it is written: the reference's radius search of each row, counting instead of pushing.
+// ... with the row's own radius (ptk.h: row i is the scalar call's row i at radius = radii[i]).
+int ptk_host_search_knn_within_radii(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint32_t k,
+                                     const float* radii, ptk_neighbor* out) {
+  if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || out == nullptr)))
+    return fail(PTK_ERR_INVALID, "null argument");
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (nq == 0) return PTK_OK;
+  const int rc = check_radii(radii, nq, /*host_values=*/true);
+  if (rc != PTK_OK) return rc;
+  return ptk_host::knn_within_rows(t, points, q, nq, k, out, [radii](uint64_t i) { return radii[i]; });
+}
+
 int ptk_host_search_count_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius,
                                  uint64_t max_count, uint64_t* counts) {
   if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || counts == nullptr)))
     return fail(PTK_ERR_INVALID, "null argument");
   if (!(radius >= 0.0f)) return fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
-  try {
-    using namespace ptk_host;
-    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
-    const flat_t& flat = *flat_holder;
-    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
-    space_t space(points, t->n_points, t->dim);
-    view_t view(space);
-    rows_loop(nq, [&](uint64_t i) {
-      internal::count_visitor<float> v(radius, (std::size_t)max_count);
-      search_one(t, flat, view, q + i * t->dim, v);
-      counts[i] = v.count();
-    });
-  } catch (const std::bad_alloc&) {
-    return fail(PTK_ERR_NOMEM, "out of host memory");
-  } catch (const std::exception& ex) {
-    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
-  }
-  return PTK_OK;
+  return ptk_host::count_within_rows(t, points, q, nq, max_count, counts, [radius](uint64_t) { return radius; });
+}
+
+int ptk_host_search_count_within_radii(const ptk_tree* t, const float* points, const float* q, uint64_t nq,
+                                       const float* radii, uint64_t max_count, uint64_t* counts) {
+  if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || counts == nullptr)))
+    return fail(PTK_ERR_INVALID, "null argument");
+  if (nq == 0) return PTK_OK;
+  const int rc = check_radii(radii, nq, /*host_values=*/true);
+  if (rc != PTK_OK) return rc;
+  return ptk_host::count_within_rows(t, points, q, nq, max_count, counts, [radii](uint64_t i) { return radii[i]; });
 }
 
 int ptk_host_search_radius(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius, float e,

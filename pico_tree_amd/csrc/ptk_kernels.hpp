@@ -1232,6 +1232,61 @@ __global__ __launch_bounds__(BLOCK) void knn_within_kernel(
   }
 }
 
+// search_knn_within_radii / count_within_radii (ptk.h): a radius per query row.  Each lane reads radii[qi] -- qi the row in
+// the CALLER's order, behind `perm`, never the launch position -- and derives the seed of its list from it as the host's
+// within_seed() (ptk_backend.hip) does for the scalar call: r * (1 + 2^-10); FLT_MAX -- unseeded -- when the metric's box
+// distance is no lower bound or the tree is of the deep stack class (`unseeded`: per call), for a subnormal radius and
+// when the product is not finite (+inf, NaN: such a row is masked to all padding when it is stored).
+__device__ __forceinline__ float within_seed_row(float r, bool unseeded) {
+  const uint32_t e = __float_as_uint(r) & 0x7F800000u;
+  if (unseeded || (r != 0.0f && (e == 0u || e == 0x7F800000u))) return 3.402823466e+38f;
+  const float s = f_mul(r, 1.0f + 0x1p-10f);
+  return (__float_as_uint(s) & 0x7F800000u) != 0x7F800000u ? s : 3.402823466e+38f;
+}
+
+// knn_within_kernel with the lane's own radius (a copy: the scalar call's kernels must compile to the code they are --
+// a change to one belongs in both).
+template <int S, int OVF, int BLOCK, int LEAFB, bool LIST_LDS, class M = MetricL2>
+__global__ __launch_bounds__(BLOCK) void knn_within_radii_kernel(
+    DevTree t, const float* __restrict__ queries, uint32_t dim,
+    const uint32_t* __restrict__ perm, uint64_t nq, uint32_t k, Neighbor* __restrict__ out,
+    const float* __restrict__ radii, uint32_t unseeded) {
+  const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
+  const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];  // (the row in the caller's order, not the launch position)
+  float qx, qy, qz;
+  load_query(queries, dim, qi, qx, qy, qz);
+  pad_query<M>(dim, qy, qz);
+
+  PTK_STACK(S, OVF, BLOCK, st, t);
+  KnnPolicy<LIST_LDS> pol;
+  if constexpr (LIST_LDS) {
+    pol.list = (LdsWord*)(ptk_smem + (size_t)S * BLOCK * 8) + threadIdx.x;
+    pol.stride = BLOCK;
+  } else {
+    pol.list = out + qi * k;
+    pol.stride = 1;
+  }
+  pol.k = k;
+  pol.filled = 0;
+  pol.worst = within_seed_row(radius, unseeded != 0u);
+  pol.e_inv = 1.0f;
+  traverse<LEAFB, false, M>(t, qx, qy, qz, pol, st);
+
+  Neighbor* row = out + qi * k;
+  for (uint32_t j = 0; j < k; ++j) {
+    Neighbor nb;
+    if (j < pol.filled) nb = pol.get(j);
+    if (j >= pol.filled || !(nb.distance < radius)) {  // never filled, or not below the radius: the pad
+      nb.index = -1;
+      nb.distance = radius;
+    }
+    row[j] = nb;
+  }
+}
+
 // (experiments: -DPTK_KNN_WAVES=n asks the compiler to fit n wavefronts per SIMD)
 #if defined(PTK_KNN_WAVES) && defined(__HIP_DEVICE_COMPILE__)
 #define PTK_KNN_REG_WAVES __attribute__((amdgpu_waves_per_eu(PTK_KNN_WAVES, PTK_KNN_WAVES)))
@@ -1336,6 +1391,81 @@ __global__ __launch_bounds__(BLOCK) PTK_KNN_REG_WAVES void knn_reg_within_kernel
   pol.init(k, 1.0f);
   pol.seed(seed);
   traverse<LEAFB, false, M>(t, qx, qy, qz, pol, st);
+  pol.mask(radius);
+#if defined(__HIP_DEVICE_COMPILE__)
+  // Full lists of a full wavefront leave through the LDS the stack no longer needs: a lane's K entries are one
+  // row of K x 8 bytes, and K lanes write it with ONE store (whole 64-byte sectors) instead of each lane writing
+  // 8 bytes of its own row K times over (64 partial lines per store: 1.83 GB of WRITE_SIZE for 0.92 GB of rows at
+  // knn = 16).  Slot (lane, j) sits at lane * K + ((j + lane) % K): the writes and the reads are conflict-free.
+  if constexpr (BLOCK == 64 && K <= S && (K & (K - 1)) == 0 && K >= 2) {
+    if (k == (uint32_t)K && (uint64_t)tile * 64u + 63u < nq) {  // (uniform)
+      LdsWord* rows = (LdsWord*)ptk_smem;
+      const uint32_t lane = threadIdx.x;
+      __syncthreads();  // (one wavefront: every lane is out of the traversal before its stack slots are reused)
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        Neighbor nb;
+        nb.index = pol.li[j];
+        nb.distance = pol.ld[j];
+        rows[lane * K + (((uint32_t)j + lane) & (K - 1))] = pack_neighbor(nb);
+      }
+      unsigned long long* __restrict__ dst = reinterpret_cast<unsigned long long*>(out);
+      if ((reinterpret_cast<uintptr_t>(out) & 15u) == 0u) {  // (uniform)
+        // Two entries -- 16 bytes -- per lane, K / 2 lanes to a row: a store instruction writes 128 / K whole rows.
+        // (With 8 bytes per lane the rows left as twice their size in WRITE_SIZE: 1.83 GB for the 0.92 GB of config 3.)
+        constexpr uint32_t kLanesPerRow = K / 2, kRowsPerStore = 64u / kLanesPerRow;
+        const uint32_t e2 = lane % kLanesPerRow, sub = lane / kLanesPerRow;
+#pragma unroll
+        for (uint32_t r0 = 0; r0 < 64u; r0 += kRowsPerStore) {
+          const uint32_t r = r0 + sub;  // the lane whose row this is
+          const uint32_t q_r = (uint32_t)__shfl((int)(uint32_t)qi, (int)r);
+          RowPair two;
+          two.a = rows[r * K + ((2u * e2 + r) & (K - 1))];
+          two.b = rows[r * K + ((2u * e2 + 1u + r) & (K - 1))];
+          *reinterpret_cast<RowPair*>(dst + (uint64_t)q_r * K + 2u * e2) = two;
+        }
+      } else {
+        constexpr uint32_t kRowsPerStore = 64u / K;
+        const uint32_t e = lane & (K - 1), sub = lane / K;
+#pragma unroll
+        for (uint32_t r0 = 0; r0 < 64u; r0 += kRowsPerStore) {
+          const uint32_t r = r0 + sub;  // the lane whose row this is
+          const uint32_t q_r = (uint32_t)__shfl((int)(uint32_t)qi, (int)r);
+          dst[(uint64_t)q_r * K + e] = rows[r * K + ((e + r) & (K - 1))];
+        }
+      }
+      PTK_TRACE_END();
+      return;
+    }
+  }
+#endif
+  pol.store(out + qi * k);
+}
+
+// knn_reg_within_kernel with the lane's own radius (a third copy of the write-out, for the reason given above).
+template <int K, int S, int OVF, int BLOCK, int LEAFB, class M = MetricL2>
+__global__ __launch_bounds__(BLOCK) PTK_KNN_REG_WAVES void knn_reg_within_radii_kernel(
+    DevTree t, const float* __restrict__ queries, uint32_t dim,
+    const uint32_t* __restrict__ perm, uint64_t nq, uint32_t k, Neighbor* __restrict__ out,
+    const float* __restrict__ radii, uint32_t unseeded) {
+  PTK_TRACE_BEGIN();
+  const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
+  const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];  // (the row in the caller's order, not the launch position)
+  float qx, qy, qz;
+  load_query(queries, dim, qi, qx, qy, qz);
+  pad_query<M>(dim, qy, qz);
+  Record spill[OVF > 0 ? OVF : 1];
+  Stack<S, OVF, BLOCK> st;
+  st.init((LdsWord*)ptk_smem, threadIdx.x, spill);
+  KnnRegPolicy<K> pol;
+  pol.init(k, 1.0f);
+  pol.seed(within_seed_row(radius, unseeded != 0u));
+  traverse<LEAFB, false, M>(t, qx, qy, qz, pol, st);
+  // (masked here, with the lane's OWN radius, while the list is in the lane's registers: in the write-out below lanes
+  // store one another's rows -- only `qi` is exchanged -- and what reaches LDS must be final)
   pol.mask(radius);
 #if defined(__HIP_DEVICE_COMPILE__)
   // Full lists of a full wavefront leave through the LDS the stack no longer needs: a lane's K entries are one

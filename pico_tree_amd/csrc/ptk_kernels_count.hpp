@@ -305,6 +305,166 @@ __global__ __launch_bounds__(BLOCK) void count_within_kernel(
   counts[qi] = count < limit ? count : limit;
 }
 
+// count_within_radii (ptk.h): count_within_kernel with the lane's own radius, radii[qi] (a copy: the scalar call's kernel
+// stays the code it is -- a change to one belongs in both).  A NaN or negative radius passes no test: the count is 0.
+template <int S, int OVF, int BLOCK, int LEAFB, class M = MetricL2>
+__global__ __launch_bounds__(BLOCK) void count_within_radii_kernel(
+    DevTree t, const CountBox* __restrict__ table, const float* __restrict__ queries, uint32_t dim,
+    const uint32_t* __restrict__ perm, uint64_t nq, const float* __restrict__ radii, uint64_t max_count,
+    uint32_t shortcut,
+    uint64_t* __restrict__ counts, uint32_t* __restrict__ stats = nullptr) {
+  const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
+  const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];  // (the row in the caller's order; `normal_r` below is the lane's with it)
+  float qx, qy, qz;
+  load_query(queries, dim, qi, qx, qy, qz);
+  pad_query<M>(dim, qy, qz);
+  // The shortcuts: a finite query row (real axes), and for the inside test a radius that is not subnormal.
+  const bool finite_q = is_finite_f(qx) && (dim < 2 || is_finite_f(qy)) && (dim < 3 || is_finite_f(qz));
+  const bool try_box = shortcut != 0u && finite_q;
+  const bool normal_r = radius == 0.0f || (__float_as_uint(radius) & 0x7F800000u) != 0u;
+  const uint64_t limit = max_count != 0u ? max_count : ~0ull;
+
+  PTK_STACK(S, OVF, BLOCK, st, t);
+  const uint4* __restrict__ nodes = t.nodes;
+  const float4* __restrict__ pts = t.pts;
+  uint32_t ref = t.root_ref;
+  float nbd = 0.0f, off0 = 0.0f, off1 = 0.0f, off2 = 0.0f;
+  uint64_t count = 0;
+  bool test = try_box;  // the root, then every far child as it is entered
+
+  for (;;) {
+    while (!(ref & kLeafBit)) {
+      const uint32_t idx = ref & kBranchIdxMask;
+      const uint4 nd = nodes[idx];  // (issued with the table entry: one round trip for both)
+      if (test) {
+        test = false;
+        const CountBox bx = table[idx];
+        const float lo[3] = {bx.lo.x, bx.lo.y, bx.lo.z}, hi[3] = {bx.hi.x, bx.hi.y, bx.hi.z};
+        const float q[3] = {qx, qy, qz}, off[3] = {off0, off1, off2};
+        bool finite_b = true;
+        float outside = 0.0f, inside = 0.0f;
+#pragma unroll
+        for (uint32_t a = 0; a < 3; ++a) {
+          if (a < dim) {
+            finite_b = finite_b && is_finite_f(lo[a]) && is_finite_f(hi[a]);
+            const float dl = M::one(f_sub(lo[a], q[a])), dh = M::one(f_sub(hi[a], q[a]));
+            const float s = (q[a] >= lo[a] && q[a] <= hi[a]) ? 0.0f : (dl < dh ? dl : dh);
+            // (the metric's own accumulation: from the first axis, as point_distance3)
+            outside = a == 0 ? s : (M::kMin ? (s < outside ? s : outside)
+                                            : (std::is_same<M, MetricLInf>::value ? (outside < s ? s : outside) : f_add(outside, s)));
+            const float ta = dl < dh ? dh : dl;
+            const float u = ta < off[a] ? off[a] : ta;
+            inside = a == 0 ? u : f_add(inside, u);
+          }
+        }
+        if (finite_b) {
+          if (outside >= radius) {
+            if (stats != nullptr) atomicAdd(&stats[kCountStatOutside], 1u);
+            ref = kLeafBit;  // (an empty leaf: on to the unwind)
+            break;
+          }
+          if (is_finite_f(inside) && f_add(inside, f_mul(inside, 0x1p-10f)) < radius) {
+            if (normal_r) {
+              if (stats != nullptr) atomicAdd(&stats[kCountStatInside], 1u);
+              count += __float_as_uint(bx.lo.w);
+              ref = kLeafBit;
+              break;
+            }
+            if (stats != nullptr) atomicAdd(&stats[kCountStatSubnormal], 1u);
+          }
+        }
+      }
+      const uint32_t axis = (ref >> 29) & 3u;
+      const float left_max = __uint_as_float(nd.x);
+      const float right_min = __uint_as_float(nd.y);
+      const float v = sel3(axis, qx, qy, qz);
+      const float s = f_sub(f_sub(f_add(left_max, right_min), v), v);
+      const bool go_left = s > 0.0f;
+      const float plane = go_left ? right_min : left_max;
+      const float new_off = M::one(f_sub(plane, v));
+      const float far_nbd = f_add(f_sub(nbd, sel3(axis, off0, off1, off2)), new_off);
+      if (radius >= far_nbd) st.push(idx | (axis << 28) | (go_left ? kRecSide : 0u), far_nbd);
+      ref = go_left ? nd.z : nd.w;
+    }
+
+    {  // the leaf, as radius_kernel scans it
+      const uint32_t lv = ref & 0x7FFFFFFFu;
+      const uint32_t begin = lv >> t.cbits;
+      const uint32_t n = lv & t.cmask;
+      for (uint32_t j = 0; j < n; j += LEAFB) {
+        float4 p[LEAFB];
+#pragma unroll
+        for (int u = 0; u < LEAFB; ++u) p[u] = pts[begin + j + u];
+#pragma unroll
+        for (int u = 0; u < LEAFB; ++u) {
+          if (j + u < n) {
+            const float d = point_distance3<M>(f_sub(qx, p[u].x), f_sub(qy, p[u].y), f_sub(qz, p[u].z));
+            count += radius > d ? 1u : 0u;  // strict
+          }
+        }
+      }
+    }
+    if (count >= limit) break;
+
+    // Back up to the next far child still worth entering (traverse<>'s unwind: one batch of kUnwind records per turn,
+    // so that a lane with a long way back up does not hold the wavefront here).
+    uint32_t enter_meta = 0;
+    float enter_val = 0.0f;
+    bool enter = false;
+    {
+      if (st.empty()) break;
+      Record rr[decltype(st)::kUnwind];
+      const int got = st.peek(rr);
+      int used = 0;
+#pragma unroll
+      for (int k = 0; k < decltype(st)::kUnwind; ++k) {
+        if (!enter && k < got) {
+          used = k + 1;
+          const float val = __uint_as_float(rr[k].y);
+          if (rr[k].x & kRecUndo) {
+            if (rr[k].x & kRecSide) {
+              nbd = val;
+            } else {
+              const uint32_t axis = (rr[k].x >> 28) & 3u;
+              off0 = axis == 0 ? val : off0;
+              off1 = axis == 1 ? val : off1;
+              off2 = axis == 2 ? val : off2;
+            }
+          } else if (radius >= val) {  // search.hpp:99
+            enter = true;
+            enter_meta = rr[k].x;
+            enter_val = val;
+          }
+        }
+      }
+      st.drop(used);
+    }
+    if (!enter) {
+      if (st.empty()) break;
+      ref = kLeafBit;
+      continue;
+    }
+    const uint32_t idx = enter_meta & kRecIdxMask;
+    const uint32_t axis = (enter_meta >> 28) & 3u;
+    const bool far_is_right = (enter_meta & kRecSide) != 0;
+    const uint4 nd = nodes[idx];
+    const float plane = far_is_right ? __uint_as_float(nd.y) : __uint_as_float(nd.x);
+    const float new_off = M::one(f_sub(plane, sel3(axis, qx, qy, qz)));
+    st.push(kRecUndo | (axis << 28), sel3(axis, off0, off1, off2));
+    st.push(kRecUndo | kRecSide, nbd);
+    off0 = axis == 0 ? new_off : off0;
+    off1 = axis == 1 ? new_off : off1;
+    off2 = axis == 2 ? new_off : off2;
+    nbd = enter_val;
+    test = try_box;
+    ref = far_is_right ? nd.w : nd.z;
+  }
+  counts[qi] = count < limit ? count : limit;
+}
+
 // counts[i] = min(counts[i], max_count): the count kernels of the other families (no limit of their own).
 PTK_GLOBAL void clamp_counts_kernel(uint64_t* __restrict__ counts, uint64_t n, uint64_t max_count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

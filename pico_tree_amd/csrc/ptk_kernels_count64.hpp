@@ -259,4 +259,145 @@ __global__ __launch_bounds__(64) void count64_within_kernel(
   counts[qi] = count < limit ? count : limit;
 }
 
+// search64_count_within_radii: count64_within_kernel with the lane's own radius, radii[qi] (a copy, as
+// count_within_radii_kernel).
+template <class M>
+__global__ __launch_bounds__(64) void count64_within_radii_kernel(
+    DevTree64 t, const CountBox64* __restrict__ table, const double* __restrict__ queries,
+    const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq, const double* __restrict__ radii, uint64_t max_count,
+    uint32_t shortcut,
+    uint64_t* __restrict__ counts, Rec64* __restrict__ stack, uint32_t slots, uint32_t* __restrict__ stats = nullptr) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  const double radius = radii[qi];
+  const uint32_t dim = t.dim;
+  const double* row = queries + qi * dim;
+  const double qx = row[0];
+  // (a missing axis: zero like the points' for sums and maxima, +inf for the minimum of metric_lninf)
+  const double qy = dim > 1 ? row[1] : metric64_pad<M>();
+  const double qz = dim > 2 ? row[2] : metric64_pad<M>();
+  const bool finite_q = is_finite_d(qx) && (dim < 2 || is_finite_d(qy)) && (dim < 3 || is_finite_d(qz));
+  const bool try_box = shortcut != 0u && finite_q;
+  const bool normal_r = radius == 0.0 || (__double_as_longlong(radius) & 0x7FF0000000000000ll) != 0;
+  const uint64_t limit = max_count != 0u ? max_count : ~0ull;
+
+  Stack64 st;
+  st.init(0, 0, stack, slots);
+  const Node64* __restrict__ nodes = t.nodes;
+  const double* __restrict__ pts = t.pts;
+  const uint32_t last = t.n_points - 1;
+  uint32_t ref = t.root_ref;
+  double nbd = 0.0, o0 = 0.0, o1 = 0.0, o2 = 0.0;
+  uint64_t count = 0;
+  bool test = try_box;
+
+  for (;;) {
+    while (!(ref & kLeafBit)) {
+      const Node64 nd = nodes[ref];
+      if (test) {
+        test = false;
+        const CountBox64 bx = table[ref];
+        const double lo[3] = {bx.lo.x, bx.lo.y, bx.lo.z}, hi[3] = {bx.hi.x, bx.hi.y, bx.hi.z};
+        const double q[3] = {qx, qy, qz}, off[3] = {o0, o1, o2};
+        bool finite_b = true;
+        double outside = 0.0, inside = 0.0;
+#pragma unroll
+        for (uint32_t a = 0; a < 3; ++a) {
+          if (a < dim) {
+            finite_b = finite_b && is_finite_d(lo[a]) && is_finite_d(hi[a]);
+            const double dl = M::one(d_sub(lo[a], q[a])), dh = M::one(d_sub(hi[a], q[a]));
+            const double s = (q[a] >= lo[a] && q[a] <= hi[a]) ? 0.0 : (dl < dh ? dl : dh);
+            outside = a == 0 ? s : (M::kMin ? (s < outside ? s : outside)
+                                            : (std::is_same<M, Metric64LInf>::value ? (outside < s ? s : outside) : d_add(outside, s)));
+            const double ta = dl < dh ? dh : dl;
+            const double u = ta < off[a] ? off[a] : ta;
+            inside = a == 0 ? u : d_add(inside, u);
+          }
+        }
+        if (finite_b) {
+          if (outside >= radius) {
+            if (stats != nullptr) atomicAdd(&stats[kCountStatOutside], 1u);
+            ref = kLeafBit;
+            break;
+          }
+          if (is_finite_d(inside) && d_add(inside, d_mul(inside, 0x1p-10)) < radius) {
+            if (normal_r) {
+              if (stats != nullptr) atomicAdd(&stats[kCountStatInside], 1u);
+              count += (uint64_t)__double_as_longlong(bx.lo.w);
+              ref = kLeafBit;
+              break;
+            }
+            if (stats != nullptr) atomicAdd(&stats[kCountStatSubnormal], 1u);
+          }
+        }
+      }
+      const double v = sel3d(nd.axis, qx, qy, qz);
+      const bool go_left = d_sub(d_sub(d_add(nd.left_max, nd.right_min), v), v) > 0.0;  // search.hpp:76
+      const double new_off = M::one(d_sub(go_left ? nd.right_min : nd.left_max, v));
+      const double far_nbd = d_add(d_sub(nbd, sel3d(nd.axis, o0, o1, o2)), new_off);
+      if (radius >= far_nbd) st.push(ref | (go_left ? kRecSide : 0u), far_nbd);
+      ref = go_left ? nd.left_ref : nd.right_ref;
+    }
+    {
+      const uint32_t lv = ref & 0x7FFFFFFFu;
+      const uint32_t begin = lv >> t.cbits;
+      const uint32_t n = lv & t.cmask;
+      for (uint32_t j = 0; j < n; j += kLeaf64) {
+        double px[kLeaf64], py[kLeaf64], pz[kLeaf64];
+#pragma unroll
+        for (int u = 0; u < kLeaf64; ++u) {
+          const uint32_t pu = begin + j + u <= last ? begin + j + u : last;
+          const double4 a = *reinterpret_cast<const double4*>(pts + (uint64_t)pu * kStride64D3);
+          px[u] = a.x;
+          py[u] = a.y;
+          pz[u] = a.z;
+        }
+#pragma unroll
+        for (int u = 0; u < kLeaf64; ++u) {
+          if (j + u < n) {
+            const double d = M::acc(M::acc(M::first(d_sub(qx, px[u])), d_sub(qy, py[u])), d_sub(qz, pz[u]));
+            count += radius > d ? 1u : 0u;  // strict
+          }
+        }
+      }
+    }
+    if (count >= limit) break;
+    bool entered = false;
+    for (;;) {
+      if (st.empty()) break;
+      const Rec64 r = st.pop();
+      if (r.x & kRecUndo) {
+        if (r.x & kRecSide) {
+          nbd = r.val;
+        } else {
+          const uint32_t axis = r.x & 0x3FFFFFFFu;
+          o0 = axis == 0 ? r.val : o0;
+          o1 = axis == 1 ? r.val : o1;
+          o2 = axis == 2 ? r.val : o2;
+        }
+        continue;
+      }
+      if (radius >= r.val) {  // search.hpp:99
+        const uint32_t idx = r.x & 0x3FFFFFFFu;
+        const bool far_is_right = (r.x & kRecSide) != 0;
+        const Node64 nd = nodes[idx];
+        const double new_off = M::one(d_sub(far_is_right ? nd.right_min : nd.left_max, sel3d(nd.axis, qx, qy, qz)));
+        st.push(kRecUndo | nd.axis, sel3d(nd.axis, o0, o1, o2));
+        st.push(kRecUndo | kRecSide, nbd);
+        o0 = nd.axis == 0 ? new_off : o0;
+        o1 = nd.axis == 1 ? new_off : o1;
+        o2 = nd.axis == 2 ? new_off : o2;
+        nbd = r.val;
+        ref = far_is_right ? nd.right_ref : nd.left_ref;
+        test = try_box;
+        entered = true;
+        break;
+      }
+    }
+    if (!entered) break;
+  }
+  counts[qi] = count < limit ? count : limit;
+}
+
 }  // namespace ptk

@@ -852,6 +852,61 @@ __global__ __launch_bounds__(64) void knn64_reg_within_kernel(
   pol.store(out + qi * k);
 }
 
+// search64_knn_within_radii (ptk.h): a radius per query row, radii[qi] with qi the row in the caller's order; the seed of
+// the lane's list is the host's (ptk_search64_knn_within_device) for that radius: r * (1 + 2^-10); DBL_MAX -- unseeded --
+// when the call's metric or the tree's depth asks for it (`unseeded`), for a subnormal radius and when the product is
+// not finite.  The two kernels are copies of the two above (the scalar call's kernels stay the code they are).
+__device__ __forceinline__ double within_seed_row64(double r, bool unseeded) {
+  const unsigned long long e = (unsigned long long)__double_as_longlong(r) & 0x7FF0000000000000ull;
+  if (unseeded || (r != 0.0 && (e == 0ull || e == 0x7FF0000000000000ull))) return kDblMax;
+  const double s = d_mul(r, 1.0 + 0x1p-10);
+  return ((unsigned long long)__double_as_longlong(s) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull ? s : kDblMax;
+}
+template <class M, bool D3>
+__global__ __launch_bounds__(64) void knn64_within_radii_kernel(
+    DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,
+    uint32_t k, Neighbor64* __restrict__ out, Rec64* __restrict__ stack, uint32_t slots,
+    const double* __restrict__ radii, uint32_t unseeded) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  const double radius = radii[qi];
+  Knn64Policy pol;
+  pol.list = out + qi * k;
+  pol.k = k;
+  pol.filled = 0;
+  pol.worst = within_seed_row64(radius, unseeded != 0u);
+  pol.e_inv = 1.0;
+  search64<M, D3>(t, queries, qi, pol, stack, slots);
+  for (uint32_t j = 0; j < k; ++j) {
+    Neighbor64 nb;
+    if (j < pol.filled) nb = pol.list[j];
+    if (j >= pol.filled || !(nb.distance < radius)) {
+      nb.index = -1;
+      nb.pad_ = 0;
+      nb.distance = radius;
+    }
+    pol.list[j] = nb;
+  }
+}
+
+template <class M, int K, bool D3>
+__global__ __launch_bounds__(64) void knn64_reg_within_radii_kernel(
+    DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,
+    uint32_t k, Neighbor64* __restrict__ out, Rec64* __restrict__ stack, uint32_t slots,
+    const double* __restrict__ radii, uint32_t unseeded) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  const double radius = radii[qi];
+  Knn64RegPolicy<K> pol;
+  pol.init(k, 1.0);
+  pol.seed(within_seed_row64(radius, unseeded != 0u));
+  search64<M, D3>(t, queries, qi, pol, stack, slots);
+  pol.mask(radius);
+  pol.store(out + qi * k);
+}
+
 template <class M, bool FILL, bool D3>
 __global__ __launch_bounds__(64) void radius64_kernel(
     DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,

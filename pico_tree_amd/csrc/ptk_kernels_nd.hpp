@@ -204,6 +204,44 @@ __global__ __launch_bounds__(64) void knn_nd_within_kernel(
   }
 }
 
+// search_knn_within_radii: knn_nd_within_kernel with the lane's own radius, radii[qi] (knn_within_radii_kernel,
+// ptk_kernels.hpp; a copy, as there).
+template <int S, int OVF, bool LIST_LDS, class M = MetricL2>
+__global__ __launch_bounds__(64) void knn_nd_within_radii_kernel(
+    DevTreeND t, const float* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t nq, uint32_t k,
+    Neighbor* __restrict__ out, const float* __restrict__ radii, uint32_t unseeded) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];
+  LdsFloat *q, *off;
+  stage_query_nd<S>(queries, t.dim, qi, q, off);
+  PTK_STACK(S, OVF, 64, st, t);
+  KnnPolicy<LIST_LDS> pol;
+  if constexpr (LIST_LDS) {
+    pol.list = (LdsWord*)(ptk_smem + (size_t)S * 64 * 8 + (size_t)t.dim * 64 * 8) + threadIdx.x;
+    pol.stride = 64;
+  } else {
+    pol.list = out + qi * k;
+    pol.stride = 1;
+  }
+  pol.k = k;
+  pol.filled = 0;
+  pol.worst = within_seed_row(radius, unseeded != 0u);
+  pol.e_inv = 1.0f;
+  traverse_nd<M>(t, q, off, 64u, pol, st);
+  Neighbor* row = out + qi * k;
+  for (uint32_t j = 0; j < k; ++j) {
+    Neighbor nb;
+    if (j < pol.filled) nb = pol.get(j);
+    if (j >= pol.filled || !(nb.distance < radius)) {
+      nb.index = -1;
+      nb.distance = radius;
+    }
+    row[j] = nb;
+  }
+}
+
 // k <= K <= 32: the k-list in registers (KnnRegPolicy, ptk_kernels.hpp).
 template <int K, int S, int OVF, class M = MetricL2>
 __global__ __launch_bounds__(64) void knn_nd_reg_kernel(
@@ -239,6 +277,28 @@ __global__ __launch_bounds__(64) void knn_nd_reg_within_kernel(
   KnnRegPolicy<K> pol;
   pol.init(k, 1.0f);
   pol.seed(seed);
+  traverse_nd<M>(t, q, off, 64u, pol, st);
+  pol.mask(radius);
+  pol.store(out + qi * k);
+}
+
+// search_knn_within_radii: knn_nd_reg_within_kernel with the lane's own radius.
+template <int K, int S, int OVF, class M = MetricL2>
+__global__ __launch_bounds__(64) void knn_nd_reg_within_radii_kernel(
+    DevTreeND t, const float* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t nq, uint32_t k,
+    Neighbor* __restrict__ out, const float* __restrict__ radii, uint32_t unseeded) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];
+  LdsFloat *q, *off;
+  stage_query_nd<S>(queries, t.dim, qi, q, off);
+  Record spill[OVF > 0 ? OVF : 1];
+  Stack<S, OVF, 64> st;
+  st.init((LdsWord*)ptk_smem, threadIdx.x, spill);
+  KnnRegPolicy<K> pol;
+  pol.init(k, 1.0f);
+  pol.seed(within_seed_row(radius, unseeded != 0u));
   traverse_nd<M>(t, q, off, 64u, pol, st);
   pol.mask(radius);
   pol.store(out + qi * k);

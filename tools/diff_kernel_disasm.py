@@ -6,12 +6,14 @@
 Each directory is a pico_tree_amd/csrc/_obj of a build.  The device code object of every unit is taken out of the
 object's .hip_fatbin section (clang-offload-bundler), disassembled (llvm-objdump) and split per symbol; branch-target
 comments are dropped.  Prints, per unit, the symbols of the old build that are missing in the new one, those only in
-the new one, and every symbol whose instructions differ.  Exit status 1 if a symbol of the old build is missing or
+the new one, and every symbol whose instructions differ, and closes each unit with the size (instructions) and one
+SHA-256 over the old build's symbols as each build has them.  Exit status 1 if a symbol of the old build is missing or
 differs.
 """
 from __future__ import annotations
 
 import glob
+import hashlib
 import os
 import re
 import subprocess
@@ -60,6 +62,13 @@ def main() -> int:
                   f"{len([s for s in b if s not in a])} new")
             for s in missing + differ:
                 print("  ", "missing" if s in missing else "differs", s)
+            for name, funcs in (("old", a), ("new", b)):
+                h, n = hashlib.sha256(), 0
+                for sym in sorted(a):
+                    body = funcs.get(sym, [])
+                    n += len(body)
+                    h.update(sym.encode() + b"\0" + "\n".join(body).encode() + b"\0")
+                print(f"   {name}: {n} instructions in these symbols, sha256 {h.hexdigest()[:32]}")
             bad += len(missing) + len(differ)
     return 1 if bad else 0
 
