@@ -225,6 +225,10 @@ struct ptk_api<float> {
                     std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius(t, q, nq, r, e, sort, offsets, out);
   }
+  static int radius_radii(tree const* t, float const* q, std::uint64_t nq, float const* radii, int sort,
+                          std::uint64_t* offsets, neighbor** out) {
+    return ptk_search_radius_radii(t, q, nq, radii, sort, offsets, out);
+  }
   static int box(tree const* t, float const* lo, float const* hi, std::uint64_t nb, std::uint64_t* offsets,
                  std::int32_t** out) {
     return ptk_search_box(t, lo, hi, nb, offsets, out);
@@ -257,6 +261,10 @@ struct ptk_api<double> {
   static int radius(tree const* t, double const* q, std::uint64_t nq, double r, double e, int sort,
                     std::uint64_t* offsets, neighbor** out) {
     return ptk_search64_radius(t, q, nq, r, e, sort, offsets, out);
+  }
+  static int radius_radii(tree const* t, double const* q, std::uint64_t nq, double const* radii, int sort,
+                          std::uint64_t* offsets, neighbor** out) {
+    return ptk_search64_radius_radii(t, q, nq, radii, sort, offsets, out);
   }
   static int box(tree const* t, double const* lo, double const* hi, std::uint64_t nb, std::uint64_t* offsets,
                  std::int32_t** out) {

@@ -409,6 +409,45 @@ class kd_tree {
     std::copy(src, src + flat.size(), flat.data());
   }
 
+  //! A radius per query row: out[i] = search_radius(query i, radii[i]) -- row i
+  //! of the member above with radius = radii[i], exact (no e), sorted ascending
+  //! by distance when \p sort.  radii.size() must be the number of queries
+  //! (std::invalid_argument otherwise), every entry >= 0 and not NaN.  Served
+  //! by the backend where count_within with a vector of radii is; where it
+  //! refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined (no backend linked), by a loop over the
+  //! single-query member.
+  template <typename QuerySpace_>
+  inline void search_radius(
+      QuerySpace_ const& queries,
+      std::vector<scalar_type> const& radii,
+      std::vector<std::vector<neighbor_type>>& out,
+      bool const sort = false) const {
+    std::vector<std::uint64_t> offsets;
+    std::vector<neighbor_type> flat;
+    if (batched_radius_radii(queries, radii, offsets, flat, &out, sort)) return;
+    out.resize(offsets.size() - 1);
+    for (size_type i = 0; i + 1 < offsets.size(); ++i) {
+      out[i].assign(flat.begin() + offsets[i], flat.begin() + offsets[i + 1]);
+    }
+  }
+
+  //! ... in the flat ragged form: row i is flat[offsets[i] .. offsets[i + 1]).
+  template <typename QuerySpace_>
+  inline void search_radius(
+      QuerySpace_ const& queries,
+      std::vector<scalar_type> const& radii,
+      std::vector<std::uint64_t>& offsets,
+      std::vector<neighbor_type>& flat,
+      bool const sort = false) const {
+    std::vector<std::vector<neighbor_type>> per_row;
+    if (!batched_radius_radii(queries, radii, offsets, flat, &per_row, sort)) return;
+    offsets.assign(per_row.size() + 1, 0);
+    for (size_type i = 0; i < per_row.size(); ++i) offsets[i + 1] = offsets[i] + per_row[i].size();
+    flat.resize(offsets.back());
+    for (size_type i = 0; i < per_row.size(); ++i) std::copy(per_row[i].begin(), per_row[i].end(), flat.data() + offsets[i]);
+  }
+
   //! Batched box search: row i (flat[offsets[i] .. offsets[i + 1])) lists the indices inside the
   //! closed box [mins[i], maxs[i]], in the traversal order of the per-query search_box.
   template <typename BoxSpace_>
@@ -678,6 +717,55 @@ class kd_tree {
       internal::warn_host_loop(refused.what());
       rows_loop();
     }
+#endif
+  }
+
+  //! search_radius with a radius per row.  The backend's answer goes to {offsets, flat} (returns false); the loop over
+  //! the single-query member -- a refused call under allow_host_loop, a PICO_TREE_HOST_ONLY build -- to per_row (true).
+  template <typename QuerySpace_>
+  bool batched_radius_radii(
+      QuerySpace_ const& queries,
+      std::vector<scalar_type> const& radii,
+      std::vector<std::uint64_t>& offsets,
+      std::vector<neighbor_type>& flat,
+      std::vector<std::vector<neighbor_type>>* per_row,
+      bool sort) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    check_radii(radii, q.rows());
+    // (the scalar member's loop with the row's own radius)
+    auto const rows_loop = [&]() {
+      per_row->assign(q.rows(), std::vector<neighbor_type>());
+      internal::host_rows_loop(q.rows(), [&](size_type i) {
+        auto x = make_row(q.data() + i * q.cols(), q.cols());
+        search_radius(x, radii[i], (*per_row)[i], sort);
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    (void)offsets;
+    (void)flat;
+    rows_loop();
+    return true;
+#else
+    offsets.assign(q.rows() + 1, 0);
+    typename api::neighbor* rows = nullptr;
+    try {
+      internal::ptk_check(
+          api::radius_radii(device(), q.data(), q.rows(), radii.data(), sort ? 1 : 0, offsets.data(), &rows),
+          "ptk_search_radius_radii");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+      return true;
+    }
+    library_rows keep(rows);  // freed even if the copy below throws
+    flat.resize(offsets.back());
+    auto const* src = reinterpret_cast<neighbor_type const*>(rows);
+    std::copy(src, src + flat.size(), flat.data());
+    return false;
 #endif
   }
 

@@ -353,6 +353,38 @@ int ptk_search_radius(const ptk_tree* tree, const float* queries, uint64_t nq,
                       float radius, float e, int sort, uint64_t* offsets,
                       ptk_neighbor** out);
 
+/* ---- radius search with a radius per query row ------------------------- */
+
+/* ptk_search_radius with `radii`, nq entries: entry i bounds query row i, in the caller's order, whatever order the
+ * batch is searched in.  Results contract: row i is, bit for bit, row i of ptk_search_radius on the same
+ * batch with radius = radii[i] and e = 1 -- the points the reference's search_radius(q_i, radii[i]) visits with
+ * distance < radii[i] (strict: search_visitor.hpp:141), in the reference's traversal order, or with sort != 0 ascending
+ * by distance (ties in unspecified order for float32, by index for float64, as the scalar forms).  Exact only: these
+ * forms take no e.  radii are in metric units (squared for L2^2).  No row's radius changes another row.
+ * Values: 0 gives an empty row; +inf, FLT_MAX / DBL_MAX and subnormal radii are valid per row; a query row with NaN,
+ * +-Inf or overflowing coordinates gets what the reference gives it.  The host-buffer forms and the host loop scan
+ * `radii`: a NaN or negative entry is PTK_ERR_INVALID, and ptk_last_error names the first such row.  The _device form
+ * only enqueues and cannot look: there a row whose radius is NaN or negative is empty -- its count is 0 and the fill
+ * writes nothing for it -- every other row is what it would be without that row, and the call returns PTK_OK.
+ * Arguments: a null `radii`, `offsets` or `out` with nq > 0 is PTK_ERR_INVALID; the record buffer of the fill pass may be
+ * null when offsets[nq] == 0 (as ptk_search_radius_fill; the _device form cannot look at d_offsets and takes d_out as
+ * given).
+ * Where the device serves them: exactly the handles ptk_search_count_within_radii serves -- dim <= 3, the four
+ * non-topological metrics, float32 trees not of the deep stack class, float64 trees of any depth; every other handle is
+ * PTK_ERR_UNSUPPORTED with that call's messages (ptk_host_search_radius_radii serves them).
+ * The handle's radius capture (ptk_search_radius_count_device / _fill_device) is neither read nor invalidated: a per-row
+ * call between a scalar count / fill pair leaves that pair as it is.
+ *
+ * The two passes of the _device form: the count pass is ptk_search_count_within_radii_device(..., max_count = 0, ...),
+ * whose counts[i] is the length of row i; the caller scans the counts into d_offsets (nq + 1 entries, exclusive) and
+ * calls the fill pass below with the same d_queries and d_radii, unchanged in between, on the same stream. */
+int ptk_search_radius_radii_fill_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, const float* d_radii,
+                                        const uint64_t* d_offsets, ptk_neighbor* d_out, int sort, void* stream);
+/* Convenience, as ptk_search_radius: the count, the scan and the fill on the device (the radii go up beside the
+ * queries).  offsets (nq + 1, host) is filled; *out is malloc'ed by the library (free with ptk_free). */
+int ptk_search_radius_radii(const ptk_tree* tree, const float* queries, uint64_t nq, const float* radii, int sort,
+                            uint64_t* offsets, ptk_neighbor** out);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -393,6 +425,9 @@ int ptk_host_search_count_within_radii(const ptk_tree* tree, const float* points
                                        const float* radii, uint64_t max_count, uint64_t* counts);
 int ptk_host_search_radius(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
                            float e, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
+/* (the loop above with the row's own radius and e = 1: radii as for the other ptk_host_*_radii loops) */
+int ptk_host_search_radius_radii(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
+                                 const float* radii, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 
@@ -491,6 +526,9 @@ int ptk_search64_count_within_radii_device(const ptk_tree64* tree, const double*
 int ptk_search64_radius(const ptk_tree64* tree, const double* queries,
                         uint64_t nq, double radius, double e, int sort,
                         uint64_t* offsets, ptk_neighbor64** out);
+/* As ptk_search_radius_radii: radii in double; served where ptk_search64_count_within_radii is. */
+int ptk_search64_radius_radii(const ptk_tree64* tree, const double* queries, uint64_t nq, const double* radii, int sort,
+                              uint64_t* offsets, ptk_neighbor64** out);
 /* As ptk_search_box. */
 int ptk_search64_box(const ptk_tree64* tree, const double* mins,
                      const double* maxs, uint64_t nb, uint64_t* offsets,

@@ -104,6 +104,8 @@ _SIGNATURES = {
     "ptk_search_knn_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search_radius_radii_fill_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "ptk_search_radius_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_search_radius_count": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p]),
     "ptk_search_radius_fill": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_float, c_void_p,
                                        c_void_p, c_int]),
@@ -123,6 +125,7 @@ _SIGNATURES = {
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
     "ptk_host_search_knn_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
     "ptk_host_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
+    "ptk_host_search_radius_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_radius": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_float, c_int,
                                        c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_box": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -150,6 +153,7 @@ _SIGNATURES = {
     "ptk_search64_knn_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]),
     "ptk_search64_count_within_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     "ptk_search64_count_within_radii_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_radius_radii": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_search64_radius": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_double, c_int, c_void_p,
                                     POINTER(c_void_p)]),
     "ptk_search64_box": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, POINTER(c_void_p)]),
@@ -1043,7 +1047,15 @@ class KdTree:
 
         A query row with NaN, +-Inf or any finite value gets the row the reference gives it (a NaN or +-Inf row
         under the sum metrics: an empty one -- ``radius > distance`` is false) and changes no other row; ``radius``
-        may be ``FLT_MAX`` or ``+inf``."""
+        may be ``FLT_MAX`` or ``+inf``.
+
+        ``radius`` may also be a 1-D array of ``nq`` radii, one per query row (``ptk_search_radius_radii`` /
+        ``ptk_search64_radius_radii``): row i is the scalar call's row i at ``radius[i]``.  That form is exact -- ``e``
+        may not be given -- and a NaN or negative entry is refused by its row.  The device serves it where it serves
+        :meth:`count_within` with an array; the rest is refused (``allow_host_loop`` serves float32 trees)."""
+        radii = None if _is_scalar_radius(radius) else radius
+        if radii is not None and any(isinstance(a, (int, float, np.floating)) and not isinstance(a, bool) for a in args):
+            raise ValueError("search_radius with one radius per query is exact: e may not be given")
         e, nns, sort = self._split_optional_radius(args, sort)
         q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
         nq = q.shape[0]
@@ -1052,6 +1064,18 @@ class KdTree:
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         rows = c_void_p()
         lib = _load()
+        if radii is not None:
+            radii = self._host_radii(radii, nq)
+            self._served(self._fn("ptk_search_radius_radii")(self._h, q.ctypes.data, nq, radii.ctypes.data,
+                                                             int(bool(sort)), offsets.ctypes.data, byref(rows)),
+                         lambda lib: lib.ptk_host_search_radius_radii(self._h, self._pts.ctypes.data, q.ctypes.data, nq,
+                                                                      radii.ctypes.data, int(bool(sort)),
+                                                                      offsets.ctypes.data, byref(rows)))
+            flat = _adopt(lib, rows, int(offsets[-1]), self._neighbor)
+            if nns is None:
+                return DArray(offsets, flat)
+            nns._assign(offsets, flat)
+            return nns
         self._served(self._fn("ptk_search_radius")(self._h, q.ctypes.data, nq, self._real(radius),
                                                    self._real(e), int(bool(sort)), offsets.ctypes.data, byref(rows)),
                      lambda lib: lib.ptk_host_search_radius(self._h, self._pts.ctypes.data, q.ctypes.data, nq,
@@ -1119,8 +1143,13 @@ class KdTree:
                                               out.data_ptr(), stream))
         return offsets, out[:total]
 
-    def search_radius_device(self, q, radius: float, e: float = 1.0, sort: bool = False):
-        """Device form: returns (offsets int64 tensor [nq + 1], raw int32 tensor [total, 2])."""
+    def search_radius_device(self, q, radius: float, e: float | None = None, sort: bool = False):
+        """Device form: returns (offsets int64 tensor [nq + 1], raw int32 tensor [total, 2]).
+
+        ``radius`` may also be a float32 CUDA tensor of ``nq`` radii, one per query row: the per-row count
+        (``ptk_search_count_within_radii_device`` with ``max_count = 0``), ``torch.cumsum`` and
+        ``ptk_search_radius_radii_fill_device`` on the current stream.  That form is exact (``e`` may not be given) and
+        only enqueues: a row whose radius is NaN or negative is empty."""
         import torch
         self._float32_only("search_radius_device()")
         if q.dtype != torch.float32 or q.dim() != 2 or q.shape[1] != self._sdim:
@@ -1131,6 +1160,20 @@ class KdTree:
         lib = _load()
         stream = torch.cuda.current_stream(q.device).cuda_stream
         counts = torch.zeros(nq + 1, dtype=torch.int64, device=q.device)
+        if not _is_scalar_radius(radius):
+            if e is not None:
+                raise ValueError("search_radius_device with one radius per query is exact: e may not be given")
+            radii = self._device_radii(radius, q, nq)
+            _check(lib.ptk_search_count_within_radii_device(self._h, q.data_ptr(), nq, radii.data_ptr(), 0,
+                                                            counts.data_ptr(), stream))
+            offsets = torch.zeros(nq + 1, dtype=torch.int64, device=q.device)
+            offsets[1:] = torch.cumsum(counts[:nq], 0)
+            total = int(offsets[-1].item())
+            out = torch.empty((max(total, 1), 2), dtype=torch.int32, device=q.device)
+            _check(lib.ptk_search_radius_radii_fill_device(self._h, q.data_ptr(), nq, radii.data_ptr(), offsets.data_ptr(),
+                                                           out.data_ptr(), int(bool(sort)), stream))
+            return offsets, out[:total]
+        e = 1.0 if e is None else e
         _check(lib.ptk_search_radius_count_device(self._h, q.data_ptr(), nq, np.float32(radius),
                                                   np.float32(e), counts.data_ptr(), stream))
         offsets = torch.zeros(nq + 1, dtype=torch.int64, device=q.device)

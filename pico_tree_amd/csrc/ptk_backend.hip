@@ -2250,6 +2250,84 @@ int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radi
   return rc;
 }
 
+// ---- radius, a radius per query row (ptk.h) --------------------------------------------------
+
+// The fill pass behind ptk_search_count_within_radii_device(max_count = 0) and a scan of its counts: the same handles
+// (check_count_within_radii), the same batch order, a scratch block of the stream's own.  It never goes through
+// radius_pass_device: the handle's radius capture (Workspace::cap_*) is neither read nor invalidated.
+int ptk_search_radius_radii_fill_device(const ptk_tree* t, const float* d_q, uint64_t nq, const float* d_radii,
+                                        const uint64_t* d_offsets, ptk_neighbor* d_out, int sort, void* stream) {
+  int rc = check_radius_radii(t, d_q, nq, d_radii, d_offsets, /*host_values=*/false);
+  if (rc != PTK_OK || nq == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
+  Scratch scratch(t, s, /*per_stream=*/true);
+  uint32_t* perm = nullptr;
+  rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, ptk::kCellsDenseFirst);
+  if (rc != PTK_OK) return rc;
+  rc = ptkf::radius_radii_fill(t, d_q, perm, nq, d_radii, d_offsets, o, s);
+  if (rc == PTK_OK && sort) {
+    Timer timer(t, s);
+    const uint32_t blocks = (uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock);
+    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, nq, d_offsets, o);
+    PTK_HIP(hipGetLastError());
+    timer.stop(2, 0);
+  }
+  return rc;
+}
+
+// Convenience, as ptk_search_radius: the count, the scan and the fill on the device; the radii go up beside the queries.
+int ptk_search_radius_radii(const ptk_tree* t, const float* q, uint64_t nq, const float* radii, int sort, uint64_t* offsets,
+                            ptk_neighbor** out) {
+  if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
+  *out = nullptr;
+  int rc = check_radius_radii(t, q, nq, radii, offsets, /*host_values=*/true);
+  if (rc != PTK_OK) return rc;
+  offsets[0] = 0;
+  if (nq == 0) return PTK_OK;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  DeviceBlock d_in, d_c, d_o, d_out;
+  const size_t qbytes = (size_t)nq * t->dim * sizeof(float);
+  hipError_t he = d_in.alloc(qbytes + nq * sizeof(float));
+  if (he == hipSuccess) he = d_c.alloc((nq + 1) * 8);
+  if (he == hipSuccess) he = d_o.alloc((nq + 1) * 8);
+  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nq + 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_in.p, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(static_cast<char*>(d_in.p) + qbytes, radii, nq * sizeof(float), hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    const float* d_q = d_in.as<float>();
+    const float* d_radii = d_q + nq * t->dim;
+    uint64_t total = 0;
+    rc = ptk_search_count_within_radii_device(t, d_q, nq, d_radii, 0, d_c.as<uint64_t>(), nullptr);
+    if (rc == PTK_OK) {
+      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nq, offsets);
+      if (he == hipSuccess) {
+        total = offsets[nq];
+        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
+      }
+      if (he == hipSuccess)
+        rc = ptk_search_radius_radii_fill_device(t, d_q, nq, d_radii, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort, nullptr);
+      if (he == hipSuccess && rc == PTK_OK) {
+        *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
+        if (*out == nullptr) {
+          rc = fail(PTK_ERR_NOMEM, "out of memory");
+        } else if (total > 0) {
+          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
+        }
+      }
+    }
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  if (rc != PTK_OK && *out) {
+    std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 namespace {

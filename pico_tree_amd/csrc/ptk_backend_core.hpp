@@ -689,6 +689,19 @@ inline int check_count_within_radii(const Tree* t, const void* q, uint64_t nq, c
   return PTK_OK;
 }
 
+// search_radius_radii (ptk.h): served exactly where count_within_radii is -- its count pass is that call -- and refused
+// through the same check with the same messages.  `offsets`: the fill pass's offsets, the convenience forms' offsets.
+template <class Tree, class Real>
+inline int check_radius_radii(const Tree* t, const void* q, uint64_t nq, const Real* radii, const void* offsets,
+                              bool host_values) {
+  int rc = check_search(t, q, nq);
+  if (rc != PTK_OK || nq == 0) return rc;
+  rc = check_radii(radii, nq, host_values);
+  if (rc != PTK_OK) return rc;
+  if (offsets == nullptr) return fail(PTK_ERR_INVALID, "null offsets buffer");
+  return check_count_within_radii(t, q, nq, radii, offsets, /*host_values=*/false);  // (the values are scanned above)
+}
+
 inline float inv_ratio(float e) { return 1.0f / e; }
 
 

@@ -730,6 +730,24 @@ int launch_radius64(const ptk_tree64* t, const double* d_q, const uint32_t* perm
   return PTK_OK;
 }
 
+// search64_radius_radii: the fill pass behind ptkf::count64_within_radii(max_count = 0); dim <= 3, no topological metric
+// (check_count_within_radii has refused the rest).
+template <class M>
+int launch_radius64_radii_fill(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq,
+                               const double* d_radii, const uint64_t* d_offsets, ptk::Neighbor64* d_out, hipStream_t s,
+                               Stack64Lease& lease) {
+  const size_t smem = ptk::lds64_bytes(0, t->dim);
+  int rc = allow_lds(ptk::radius64_radii_fill_kernel<M>, smem);
+  if (rc != PTK_OK) return rc;
+  for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {
+    const uint64_t n = std::min(lease.piece, nq - q0);
+    hipLaunchKernelGGL((ptk::radius64_radii_fill_kernel<M>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q,
+                       perm, q0, n, d_radii, d_offsets, d_out, lease.stack, t->slots);
+  }
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
 template <bool FILL>
 int launch_box64(const ptk_tree64* t, const double* d_mins, const double* d_maxs, uint64_t nb, uint64_t* d_counts,
                  const uint64_t* d_offsets, int32_t* d_out, hipStream_t s, Stack64Lease& lease) {
@@ -1249,6 +1267,68 @@ int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, doubl
           rc = fail(PTK_ERR_NOMEM, "out of memory");
         } else {
           he = hipMemcpy(*out, d_out, obytes, hipMemcpyDeviceToHost);
+        }
+      }
+    }
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  if (rc != PTK_OK && *out) {
+    std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+
+// ptk_search_radius_radii in double: the per-row count (max_count = 0), the scan and the fill on the device, the radii
+// beside the queries.  The handles ptk_search64_count_within_radii serves; the rest is refused by the same check.
+int ptk_search64_radius_radii(const ptk_tree64* t, const double* q, uint64_t nq, const double* radii, int sort,
+                              uint64_t* offsets, ptk_neighbor64** out) {
+  if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
+  *out = nullptr;
+  int rc = check_radius_radii(t, q, nq, radii, offsets, /*host_values=*/true);
+  if (rc != PTK_OK) return rc;
+  offsets[0] = 0;
+  if (nq == 0) return PTK_OK;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bin, bout;
+  const size_t qbytes = (size_t)nq * t->dim * sizeof(double);
+  const size_t q_room = (qbytes + 255) & ~size_t(255), c_room = ((nq + 1) * 8 + 255) & ~size_t(255);
+  hipError_t he = bin.get(t, 0, q_room + 3 * c_room);
+  double* d_q = reinterpret_cast<double*>(bin.p);
+  double* d_r = reinterpret_cast<double*>(bin.p + q_room);
+  uint64_t* d_c = reinterpret_cast<uint64_t*>(bin.p + q_room + c_room);
+  uint64_t* d_o = reinterpret_cast<uint64_t*>(bin.p + q_room + 2 * c_room);
+  if (he == hipSuccess) he = hipMemset(d_c, 0, (nq + 1) * 8);
+  if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(d_r, radii, nq * sizeof(double), hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    rc = ptk_search64_count_within_radii_device(t, d_q, nq, d_r, 0, d_c, nullptr);
+    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, nq, offsets);
+    if (rc == PTK_OK) {
+      const size_t obytes = std::max<uint64_t>(offsets[nq], 1) * sizeof(ptk_neighbor64);
+      he = bout.get(t, 1, obytes);
+      ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(bout.p);
+      if (he == hipSuccess) he = hipMemset(d_out, 0, obytes);  // (the padding bytes of the records: no kernel writes them)
+      if (he == hipSuccess) {
+        Stack64Lease lease(t, nullptr);
+        const uint32_t* perm = nullptr;
+        rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
+        if (rc == PTK_OK)
+          PTK_WITH_EUCLID64(rc = (launch_radius64_radii_fill<M>(t, d_q, perm, nq, d_r, d_o, d_out, nullptr, lease)));
+        if (rc == PTK_OK && sort) {
+          hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock),
+                             0, nullptr, d_o, nq, d_out);
+          he = hipGetLastError();
+        }
+      }
+      if (he == hipSuccess && rc == PTK_OK) {
+        *out = static_cast<ptk_neighbor64*>(std::malloc(obytes));
+        if (*out == nullptr) {
+          rc = fail(PTK_ERR_NOMEM, "out of memory");
+        } else {
+          he = hipMemcpy(*out, bout.p, obytes, hipMemcpyDeviceToHost);
         }
       }
     }

@@ -110,6 +110,9 @@ int count_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint
                  bool shortcut, uint64_t* d_counts, hipStream_t s);
 int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
                         uint64_t max_count, bool shortcut, uint64_t* d_counts, hipStream_t s);
+// search_radius_radii (ptk.h): the rows behind count_within_radii(max_count = 0) and a scan of its counts
+int radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                      const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s);
 int clamp_counts(uint64_t* d_counts, uint64_t n, uint64_t max_count, hipStream_t s);
 // ... and of float64 trees with dim <= 3 (ptk_kernels_count64.hpp): kCountBox64Bytes per branch
 constexpr size_t kCountBox64Bytes = 64;

@@ -38,6 +38,19 @@ int launch_count_within_radii(const ptk_tree* t, const float* d_q, const uint32_
   return PTK_OK;
 }
 
+// search_radius_radii: the fill pass behind launch_count_within_radii(max_count = 0).
+template <int S, int OVF, int LEAFB, class M>
+int launch_radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                             const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((nq + 63) / 64);
+  Timer timer(t, s);
+  hipLaunchKernelGGL((ptk::radius_radii_fill_kernel<S, OVF, 64, LEAFB, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                     t->dev, d_q, t->dim, perm, nq, d_radii, d_offsets, d_out);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, nq);
+  return PTK_OK;
+}
+
 static __global__ void warm_count_kernel() {}
 
 }  // namespace
@@ -83,6 +96,14 @@ int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm
   int rc = PTK_OK;
   PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_within_radii<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, d_radii, max_count,
                                                                                   shortcut, d_counts, s))));
+  return rc;
+}
+
+int radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
+                      const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_radius_radii_fill<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, d_radii, d_offsets,
+                                                                                  d_out, s))));
   return rc;
 }
 

@@ -187,6 +187,44 @@ int count_within_rows(const ptk_tree* t, const float* points, const float* q, ui
   return PTK_OK;
 }
 
+// search_radius (ptk.h) as it is written: the reference's radius search of each row, the rows laid end to end.
+// `radius_of(i)`: the radius of row i, as knn_within_rows takes it.
+template <class RadiusOf>
+int radius_rows(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float e, int sort, uint64_t* offsets,
+                ptk_neighbor** out, RadiusOf&& radius_of) {
+  *out = nullptr;
+  try {
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    std::vector<std::vector<neighbor_t>> per_row(nq);
+    rows_loop(nq, [&](uint64_t i) {
+      if (e == 1.0f) {
+        internal::radius_visitor<neighbor_t> v(radius_of(i), per_row[i]);
+        search_one(t, flat, view, q + i * t->dim, v);
+        if (sort) v.sort();
+      } else {
+        internal::radius_visitor<neighbor_t, true> v(radius_of(i), per_row[i], e);
+        search_one(t, flat, view, q + i * t->dim, v);
+        if (sort) v.sort();
+      }
+    });
+    offsets[0] = 0;
+    for (uint64_t i = 0; i < nq; ++i) offsets[i + 1] = offsets[i] + per_row[i].size();
+    auto* rows = static_cast<neighbor_t*>(std::malloc(std::max<size_t>(offsets[nq], 1) * sizeof(neighbor_t)));
+    if (rows == nullptr) return fail(PTK_ERR_NOMEM, "out of host memory");
+    for (uint64_t i = 0; i < nq; ++i) std::copy(per_row[i].begin(), per_row[i].end(), rows + offsets[i]);
+    *out = reinterpret_cast<ptk_neighbor*>(rows);
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 }  // namespace ptk_host
 
 extern "C" {
@@ -273,38 +311,20 @@ int ptk_host_search_radius(const ptk_tree* t, const float* points, const float* 
   if (t == nullptr || points == nullptr || offsets == nullptr || out == nullptr || (nq > 0 && q == nullptr))
     return fail(PTK_ERR_INVALID, "null argument");
   if (!(e > 0.0f)) return fail(PTK_ERR_INVALID, "approximation ratio e must be > 0");
+  return ptk_host::radius_rows(t, points, q, nq, e, sort, offsets, out, [radius](uint64_t) { return radius; });
+}
+
+// ... with the row's own radius (ptk.h: row i is the scalar call's row i at radius = radii[i], e = 1).
+int ptk_host_search_radius_radii(const ptk_tree* t, const float* points, const float* q, uint64_t nq, const float* radii,
+                                 int sort, uint64_t* offsets, ptk_neighbor** out) {
+  if (t == nullptr || points == nullptr || offsets == nullptr || out == nullptr || (nq > 0 && q == nullptr))
+    return fail(PTK_ERR_INVALID, "null argument");
   *out = nullptr;
-  try {
-    using namespace ptk_host;
-    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
-    const flat_t& flat = *flat_holder;
-    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
-    space_t space(points, t->n_points, t->dim);
-    view_t view(space);
-    std::vector<std::vector<neighbor_t>> per_row(nq);
-    rows_loop(nq, [&](uint64_t i) {
-      if (e == 1.0f) {
-        internal::radius_visitor<neighbor_t> v(radius, per_row[i]);
-        search_one(t, flat, view, q + i * t->dim, v);
-        if (sort) v.sort();
-      } else {
-        internal::radius_visitor<neighbor_t, true> v(radius, per_row[i], e);
-        search_one(t, flat, view, q + i * t->dim, v);
-        if (sort) v.sort();
-      }
-    });
-    offsets[0] = 0;
-    for (uint64_t i = 0; i < nq; ++i) offsets[i + 1] = offsets[i] + per_row[i].size();
-    auto* rows = static_cast<neighbor_t*>(std::malloc(std::max<size_t>(offsets[nq], 1) * sizeof(neighbor_t)));
-    if (rows == nullptr) return fail(PTK_ERR_NOMEM, "out of host memory");
-    for (uint64_t i = 0; i < nq; ++i) std::copy(per_row[i].begin(), per_row[i].end(), rows + offsets[i]);
-    *out = reinterpret_cast<ptk_neighbor*>(rows);
-  } catch (const std::bad_alloc&) {
-    return fail(PTK_ERR_NOMEM, "out of host memory");
-  } catch (const std::exception& ex) {
-    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  if (nq > 0) {
+    const int rc = check_radii(radii, nq, /*host_values=*/true);
+    if (rc != PTK_OK) return rc;
   }
-  return PTK_OK;
+  return ptk_host::radius_rows(t, points, q, nq, 1.0f, sort, offsets, out, [radii](uint64_t i) { return radii[i]; });
 }
 
 int ptk_host_search_box(const ptk_tree* t, const float* points, const float* mins, const float* maxs, uint64_t nb,

@@ -465,6 +465,35 @@ __global__ __launch_bounds__(BLOCK) void count_within_radii_kernel(
   counts[qi] = count < limit ? count : limit;
 }
 
+// search_radius_radii (ptk.h): the fill pass behind count_within_radii_kernel(max_count = 0) and a scan of its counts --
+// radius_kernel<FILL = true> (ptk_kernels.hpp) with the lane's own radius, radii[qi], and e = 1 (a copy: the scalar
+// call's kernel stays the code it is -- a change to one belongs in both).  Row qi is written at out + offsets[qi] in the
+// reference's traversal order; neither shortcut of the count kernel is taken (the inside one cannot be: the order inside a
+// subtree depends on the query).  A NaN or negative radius -- its count was 0 -- leaves before it touches `out`.
+template <int S, int OVF, int BLOCK, int LEAFB, class M = MetricL2>
+__global__ __launch_bounds__(BLOCK) void radius_radii_fill_kernel(
+    DevTree t, const float* __restrict__ queries, uint32_t dim,
+    const uint32_t* __restrict__ perm, uint64_t nq, const float* __restrict__ radii,
+    const uint64_t* __restrict__ offsets, Neighbor* __restrict__ out) {
+  const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
+  const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[i] : i;
+  const float radius = radii[qi];  // (the row in the caller's order, not the launch position)
+  if (!(radius >= 0.0f)) return;
+  float qx, qy, qz;
+  load_query(queries, dim, qi, qx, qy, qz);
+  pad_query<M>(dim, qy, qz);
+
+  PTK_STACK(S, OVF, BLOCK, st, t);
+  RadiusPolicy<kRadiusFill> pol;
+  pol.radius = radius;
+  pol.e_inv = 1.0f;
+  pol.count = 0;
+  pol.out = out + offsets[qi];
+  traverse<LEAFB, false, M>(t, qx, qy, qz, pol, st);
+}
+
 // counts[i] = min(counts[i], max_count): the count kernels of the other families (no limit of their own).
 PTK_GLOBAL void clamp_counts_kernel(uint64_t* __restrict__ counts, uint64_t n, uint64_t max_count) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -924,6 +924,28 @@ __global__ __launch_bounds__(64) void radius64_kernel(
   if (!FILL) counts[qi] = pol.count;
 }
 
+// search64_radius_radii (ptk.h): the fill pass behind count64_within_radii_kernel(max_count = 0) and a scan of its counts --
+// radius64_kernel<FILL = true> with the lane's own radius, radii[qi] (qi the caller's row, behind `perm`), and e = 1 (a
+// copy: the scalar call's kernel stays the code it is).  dim <= 3 only, as the count: the query lives in registers.  A NaN
+// or negative radius -- its count was 0 -- leaves before it touches `out`.
+template <class M>
+__global__ __launch_bounds__(64) void radius64_radii_fill_kernel(
+    DevTree64 t, const double* __restrict__ queries, const uint32_t* __restrict__ perm, uint64_t q0, uint64_t nq,
+    const double* __restrict__ radii, const uint64_t* __restrict__ offsets, Neighbor64* __restrict__ out,
+    Rec64* __restrict__ stack, uint32_t slots) {
+  const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x) * 64 + threadIdx.x;
+  if (i >= nq) return;
+  const uint64_t qi = perm ? perm[q0 + i] : q0 + i;
+  const double radius = radii[qi];
+  if (!(radius >= 0.0)) return;
+  Radius64Policy<true> pol;
+  pol.radius = radius;
+  pol.e_inv = 1.0;
+  pol.count = 0;
+  pol.out = out + offsets[qi];
+  search64<M, true>(t, queries, qi, pol, stack, slots);
+}
+
 // Morton key of each query inside the root box (first three axes), as morton_kernel of
 // ptk_kernels.hpp: neighbouring lanes then walk neighbouring leaves.  Only the launch order depends
 // on it, never a result.
