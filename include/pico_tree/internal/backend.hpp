@@ -209,6 +209,7 @@ struct ptk_api<float> {
   static int knn_within(tree const* t, float const* q, std::uint64_t nq, std::uint32_t k, float r, neighbor* out) {
     return ptk_search_knn_within(t, q, nq, k, r, out);
   }
+  static int knn_self(tree const* t, std::uint32_t k, neighbor* out) { return ptk_search_knn_self(t, k, out); }
   static int count_within(tree const* t, float const* q, std::uint64_t nq, float r, std::uint64_t max_count,
                           std::uint64_t* counts) {
     return ptk_search_count_within(t, q, nq, r, max_count, counts);
@@ -246,6 +247,7 @@ struct ptk_api<double> {
   static int knn_within(tree const* t, double const* q, std::uint64_t nq, std::uint32_t k, double r, neighbor* out) {
     return ptk_search64_knn_within(t, q, nq, k, r, out);
   }
+  static int knn_self(tree const* t, std::uint32_t k, neighbor* out) { return ptk_search64_knn_self(t, k, out); }
   static int count_within(tree const* t, double const* q, std::uint64_t nq, double r, std::uint64_t max_count,
                           std::uint64_t* counts) {
     return ptk_search64_count_within(t, q, nq, r, max_count, counts);

@@ -23,6 +23,8 @@
 #include <fstream>
 #include <iostream>
 #include <iterator>
+#include <limits>
+#include <stdexcept>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -195,6 +197,37 @@ class kd_tree {
     knn.resize(n);
   }
 
+  //! The k nearest OTHER points of the tree's own point \p index (DESIGN.md
+  //! §2): the search_knn row of m = min(k + 1, number of points) entries for
+  //! that point with one entry removed -- the first whose index is \p index,
+  //! else (k + 1 or more other points coincide with it and are visited first)
+  //! the last; \p knn is resized to what remains (at most k entries).
+  inline void search_knn_self(
+      index_type const index, size_type const k, std::vector<neighbor_type>& knn) const {
+    auto const points = view();
+    if (index < index_type(0) || static_cast<size_type>(index) >= points.size()) {
+      throw std::out_of_range("pico_tree: search_knn_self: no such point");
+    }
+    knn.resize(std::min(k + 1, points.size()));
+    internal::knn_visitor<typename std::vector<neighbor_type>::iterator> v(knn.begin(), knn.end());
+    auto const x = make_row(points[index], points.sdim());
+    search_nearest(x, v);
+    // (only the entries the search wrote, as search_knn_within)
+    size_type const found = static_cast<size_type>(v.filled() - knn.begin());
+    size_type drop = knn.size() - 1;
+    for (size_type j = 0; j < found; ++j) {
+      if (knn[j].index == index) {
+        drop = j;
+        break;
+      }
+    }
+    size_type n = 0;
+    for (size_type j = 0; j < found; ++j) {
+      if (j != drop && knn[j].distance < std::numeric_limits<scalar_type>::max()) knn[n++] = knn[j];
+    }
+    knn.resize(n);
+  }
+
   template <typename P_, typename RandomAccessIterator_>
   inline void search_knn(
       P_ const& x,
@@ -315,6 +348,17 @@ class kd_tree {
       scalar_type const radius,
       neighbor_type* out) const {
     batched_knn_within(queries, k, radius, out);
+  }
+
+  //! Each point's k nearest other points: \p out is resized to size() * k,
+  //! out[i * k + j] is entry j of search_knn_self(i, k, ...), the row padded to
+  //! k entries with {-1, largest scalar}.  There is no query space: the
+  //! backend holds the points.  Served by the backend (ptk_search_knn_self);
+  //! where it refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined, by a loop over the per-point member.  Throws
+  //! on failure; k == 0 is std::invalid_argument.
+  inline void search_knn_self(size_type const k, std::vector<neighbor_type>& out) const {
+    batched_knn_self(k, out);
   }
 
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
@@ -643,6 +687,38 @@ class kd_tree {
         counts[i] = max_count != 0 && n > max_count ? max_count : n;
       });
     }
+  }
+
+  void batched_knn_self(size_type k, std::vector<neighbor_type>& out) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    if (k == 0) throw std::invalid_argument("pico_tree: search_knn_self: k must be >= 1");
+    size_type const n = view().size();
+    out.resize(n * k);
+    // (the per-point member, the row padded)
+    auto const rows_loop = [&]() {
+      internal::host_rows_loop(n, [&](size_type i) {
+        std::vector<neighbor_type> row;
+        search_knn_self(static_cast<index_type>(i), k, row);
+        std::copy(row.begin(), row.end(), out.begin() + i * k);
+        std::fill(
+            out.begin() + i * k + row.size(), out.begin() + (i + 1) * k,
+            neighbor_type(index_type(-1), std::numeric_limits<scalar_type>::max()));
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(
+          api::knn_self(device(), static_cast<std::uint32_t>(k), reinterpret_cast<typename api::neighbor*>(out.data())),
+          "ptk_search_knn_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
   }
 
   void check_radii(std::vector<scalar_type> const& radii, size_type rows) const {

@@ -270,6 +270,26 @@ int ptk_search_knn_within_device(const ptk_tree* tree, const float* d_queries,
                                  uint64_t nq, uint32_t k, float radius,
                                  ptk_neighbor* d_out, void* stream);
 
+/* ---- each tree point's k nearest other points ---------------------------- */
+
+/* Results contract: n_points rows of k records; row i belongs to the point with original index i.
+ * Let m = min(k + 1, n_points) and R the reference's search_knn(p_i, m) row (the same tree, the same metric, exact).
+ * Row i is R with ONE entry removed -- the first entry whose index is i if there is one, otherwise the last entry
+ * (k + 1 or more other points coincide with p_i and the reference visits them first) --, the remaining entries in
+ * their order, padded to k entries with {index = -1, distance = FLT_MAX}: k > n_points - 1, or a slot the reference
+ * never accepted (an accepted distance is always < FLT_MAX).  Same indices, same distance bits.  The search is exact
+ * (no e).  k == 0 is PTK_ERR_INVALID, a null output with n_points > 0 is PTK_ERR_INVALID, a host-only handle is
+ * PTK_ERR_DEVICE.  There is no query buffer: the handle holds every point on the device, in leaf order.
+ *   ptk_debug_self_route says which route serves (tree, k): 1 = the direct kernel (dim <= 3, the four non-topological
+ * metrics, at most 1 031 levels, k <= 63) -- the device form only enqueues on `stream`: no allocation, no wait --;
+ * 2 = the staged route (every other handle): pieces of the tree's points go through ptk_search_knn_device with k + 1
+ * and lose their own entry on the device.  That route ALLOCATES a block per call (at most 256 MiB) and WAITS for
+ * `stream` before it returns: it is not enqueue-only, and must not be called under a stream capture.  A refusal of the
+ * underlying search (PTK_ERR_UNSUPPORTED: a topological tree deeper than the device stack) is passed on unchanged;
+ * ptk_host_search_knn_self serves it.  The host form copies the rows back only: nothing is uploaded. */
+int ptk_search_knn_self(const ptk_tree* tree, uint32_t k, ptk_neighbor* out);
+int ptk_search_knn_self_device(const ptk_tree* tree, uint32_t k, ptk_neighbor* d_out, void* stream);
+
 /* ---- neighbour counts within a radius ------------------------------------ */
 
 /* Results contract: counts[i] is the length of the reference's search_radius(q_i, radius) row -- the
@@ -416,6 +436,9 @@ int ptk_host_search_knn(const ptk_tree* tree, const float* points, const float* 
                         float e, ptk_neighbor* out);
 int ptk_host_search_knn_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
                                uint32_t k, float radius, ptk_neighbor* out);
+/* (ptk_search_knn_self as it is written: the loop over the tree's own points with min(k + 1, n_points) entries and the
+ * rule; every metric, the topological ones included) */
+int ptk_host_search_knn_self(const ptk_tree* tree, const float* points, uint32_t k, ptk_neighbor* out);
 int ptk_host_search_count_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
                                  float radius, uint64_t max_count, uint64_t* counts);
 /* (the scalar loops with the row's own radius: radii has nq entries, a NaN or negative one is PTK_ERR_INVALID by its row) */
@@ -499,6 +522,10 @@ int ptk_search64_knn(const ptk_tree64* tree, const double* queries, uint64_t nq,
 int ptk_search64_knn_device(const ptk_tree64* tree, const double* d_queries,
                             uint64_t nq, uint32_t k, double e,
                             ptk_neighbor64* d_out, void* stream);
+/* As ptk_search_knn_self / ptk_search_knn_self_device (the pad: {-1, DBL_MAX}).  Every float64 tree takes the staged
+ * route: the device form allocates per call and waits for `stream`. */
+int ptk_search64_knn_self(const ptk_tree64* tree, uint32_t k, ptk_neighbor64* out);
+int ptk_search64_knn_self_device(const ptk_tree64* tree, uint32_t k, ptk_neighbor64* d_out, void* stream);
 /* As ptk_search_knn_within / ptk_search_knn_within_device (the pad: {-1, radius} in double). */
 int ptk_search64_knn_within(const ptk_tree64* tree, const double* queries, uint64_t nq,
                             uint32_t k, double radius, ptk_neighbor64* out);
@@ -692,6 +719,8 @@ int ptk_debug_batch_order(const ptk_tree* tree, int* how);
  * record stacks spill to an HBM block of at most PTK_DEEP_SPILL_MB, the batch runs in pieces of at least 64 queries);
  * 0 if the handle has made no such search. */
 int ptk_debug_deep_pieces(const ptk_tree* tree, uint32_t* pieces);
+/* Which route ptk_search_knn_self(tree, k) takes: 1 = the direct kernel, 2 = the staged route (see there). */
+int ptk_debug_self_route(const ptk_tree* tree, uint32_t k, int* route);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -96,6 +96,8 @@ _SIGNATURES = {
     "ptk_search_knn": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_search_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p,
                                       c_void_p]),
+    "ptk_search_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "ptk_search_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
     "ptk_search_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_search_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p]),
     "ptk_search_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -122,6 +124,7 @@ _SIGNATURES = {
     "ptk_free": (None, [c_void_p]),
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
+    "ptk_host_search_knn_self": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
     "ptk_host_search_knn_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
     "ptk_host_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
@@ -145,6 +148,8 @@ _SIGNATURES = {
                                                           POINTER(c_void_p)]),
     "ptk_search64_knn": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
     "ptk_search64_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
+    "ptk_search64_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "ptk_search64_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
     "ptk_search64_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
     "ptk_search64_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p]),
@@ -175,6 +180,7 @@ _SIGNATURES = {
     "ptk_debug_key_bits": (c_int, [c_void_p, c_uint64, POINTER(c_uint32)]),
     "ptk_debug_batch_order": (c_int, [c_void_p, POINTER(c_int)]),
     "ptk_debug_deep_pieces": (c_int, [c_void_p, POINTER(c_uint32)]),
+    "ptk_debug_self_route": (c_int, [c_void_p, c_uint32, POINTER(c_int)]),
     "ptk_debug_knn_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
     "ptk_debug_radius_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
     "ptk_tree64_debug_knn_coop_counts": (c_int, [c_void_p, POINTER(c_uint32)]),
@@ -923,6 +929,58 @@ class KdTree:
                                                                     np.float32(radius), rows.ctypes.data))
         if rows is not nns:
             nns.reshape(-1)[:] = rows.reshape(-1)
+        return nns
+
+    def self_route(self, k: int) -> int:
+        """Which route :meth:`search_knn_self` takes for ``k`` on this tree: 1 the direct kernel, 2 the staged route
+        (``ptk_debug_self_route``; a float64 tree always takes the staged route)."""
+        if self._f64:
+            return 2
+        route = c_int(0)
+        _check(_load().ptk_debug_self_route(self._h, int(k), byref(route)))
+        return int(route.value)
+
+    def search_knn_self(self, k: int, nns=None, device: bool = False):
+        """``search_knn_self(k[, nns], device=False)`` -- each tree point's k nearest OTHER points.
+
+        Row i belongs to point i of the tree.  It is :meth:`search_knn`'s row of ``min(k + 1, npts)`` entries for that
+        point with one entry removed -- the first whose index is i, else (``k + 1`` or more other points coincide with
+        it and come first) the last --, padded to k entries with ``(index -1, distance FLT_MAX)`` (``DBL_MAX`` for
+        float64).  Exact; float32 and float64 trees; no query array: the tree holds its points on the device
+        (``ptk_search_knn_self`` / ``ptk_search64_knn_self``).
+
+        Returns numpy rows of :attr:`dtype_neighbor`, ``(npts, k)`` or ``(npts,)`` for ``k == 1``.  With
+        ``device=True``, or a torch CUDA tensor / :class:`DeviceNeighbors` as ``nns``, the rows stay on the device
+        (a :class:`DeviceNeighbors`, on the current torch stream).  :meth:`self_route` says whether the call only
+        enqueues (1) or allocates and waits (2).
+        """
+        k = int(k)
+        n = self._npts
+        NB = self._neighbor
+        if device or isinstance(nns, DeviceNeighbors) or _is_torch(nns):
+            import torch
+            traw = torch.int64 if self._f64 else torch.int32
+            out = nns.raw if isinstance(nns, DeviceNeighbors) else nns
+            if out is None:
+                dev = torch.device("cuda", int(self.info()["device"]))
+                out = (torch.zeros if self._f64 else torch.empty)((n, max(k, 0), 2), dtype=traw, device=dev)
+            if not out.is_cuda or out.dtype != traw or tuple(out.shape) != (n, k, 2) or not out.is_contiguous():
+                raise ValueError(f"nns must be a contiguous CUDA {traw} (npts, k, 2) tensor")
+            stream = torch.cuda.current_stream(out.device).cuda_stream
+            _check(self._fn("ptk_search_knn_self_device")(self._h, k, out.data_ptr(), stream))
+            return DeviceNeighbors(out)
+        shape = (n,) if k == 1 else (n, max(k, 0))
+        if nns is None:
+            nns = np.zeros(shape, dtype=NB) if self._f64 else np.empty(shape, dtype=NB)
+        elif not isinstance(nns, np.ndarray) or nns.dtype != NB:
+            raise ValueError("unexpected dtype_neighbor for data")
+        elif nns.size != n * k or not nns.flags.c_contiguous:
+            try:
+                nns.resize(shape, refcheck=False)
+            except ValueError:
+                nns = np.zeros(shape, dtype=NB)
+        self._served(self._fn("ptk_search_knn_self")(self._h, k, nns.ctypes.data),
+                     lambda lib: lib.ptk_host_search_knn_self(self._h, self._pts.ctypes.data, k, nns.ctypes.data))
         return nns
 
     def count_within(self, pts, radius: float, max_count: int = 0):

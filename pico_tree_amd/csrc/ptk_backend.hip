@@ -295,6 +295,7 @@ struct ProcessWarmup {
       ptkf::warm_topo();
       ptkf::warm_count();
       ptkf::warm_f64();
+      ptkf::warm_self();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
     });
@@ -1920,6 +1921,72 @@ int ptk_search_knn_within_radii(const ptk_tree* t, const float* q, uint64_t nq, 
         return ptk_search_knn_within_radii_device(t, d_q, nq, k, d_radii, reinterpret_cast<ptk_neighbor*>(d_out), s);
       },
       radii, &d_radii);
+}
+
+// ---- each tree point's k nearest other points -------------------------------
+
+// Which route serves search_knn_self(k) on this handle: 1 = the direct kernel (ptk_family_self.hip, K17), 2 = the
+// staged route.  The direct kernel serves 3-D float32 trees of the four non-topological metrics and the private stack
+// classes with k + 1 <= 64; test hook self_route = 2 sends those through the staged route as well.  The rule is the
+// capability rule alone: measured on cloud L at 7.73 M and 150 k points, k = 1 / 7 / 15 / 16, the direct kernel takes
+// 0.42-0.67 / 0.19-0.37 of the staged route's time and is nowhere slower (profiles/knn_self_bench.json).
+static int self_route_of(const ptk_tree* t, uint32_t k) {
+  const bool direct = t->dim <= 3 && !topological(t) && !deep_tree(t) && k < 64u;
+  return direct && knob_int("self_route", 0) != 2 ? 1 : 2;
+}
+
+int ptk_search_knn_self_device(const ptk_tree* t, uint32_t k, ptk_neighbor* d_out, void* stream) {
+  const int rc = check_knn_self(t, k, d_out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ptk::Neighbor* out = reinterpret_cast<ptk::Neighbor*>(d_out);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  if (self_route_of(t, k) == 1) {  // (ranges of leaf positions: no scratch, nothing allocated, nothing waited for)
+    return in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) { return ptkf::knn_self(t, first, n, k, out, s); });
+  }
+  const float4* recs = t->dim <= 3 ? t->dev.pts : nullptr;
+  const int32_t* index = t->dim <= 3 ? nullptr : t->dev_nd.index;
+  return ptkf::self_staged<float, ptk_neighbor>(
+      t->n_points, t->dim, k, s,
+      [&](uint64_t first, uint64_t n, float* d_q) {
+        return ptkf::self_queries(recs, t->dev_nd.pts, t->dim, t->dim, first, n, d_q, s);
+      },
+      // (the handle's own search, refusals included -- a topological tree of the deep class -- and its own scratch lock)
+      [&](const float* d_q, uint64_t n, ptk_neighbor* d_rows) { return ptk_search_knn_device(t, d_q, n, k + 1u, 1.0f, d_rows, s); },
+      [&](const ptk_neighbor* d_rows, uint64_t first, uint64_t n) {
+        return ptkf::drop_self(reinterpret_cast<const ptk::Neighbor*>(d_rows), recs, index, first, n, k, out, s);
+      });
+}
+
+// The host form: nothing goes up -- the rows come down only (through the output block of the handle's host staging).
+int ptk_search_knn_self(const ptk_tree* t, uint32_t k, ptk_neighbor* out) {
+  const int rc = check_knn_self(t, k, out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t out_bytes = (size_t)t->n_points * k * sizeof(ptk_neighbor);
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
+  if (src != PTK_OK) return src;
+  src = ptk_search_knn_self_device(t, k, reinterpret_cast<ptk_neighbor*>(io.d_out), io.search[0]);
+  if (src != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return src;
+  }
+  PTK_HIP(hipMemcpyAsync(out, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  return PTK_OK;
+}
+
+int ptk_debug_self_route(const ptk_tree* t, uint32_t k, int* route) {
+  if (route == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  const int rc = check_knn_self(t, k, route);
+  if (rc != PTK_OK) return rc;
+  *route = self_route_of(t, k);
+  return PTK_OK;
 }
 
 // ---- neighbour counts within a radius ---------------------------------------

@@ -8,6 +8,7 @@
 //   ptk_family_nd.hip      any dimension > 3
 //   ptk_family_topo.hip    topological metrics
 //   ptk_family_f64.hip     double precision (ptk_backend_f64.hpp)
+//   ptk_family_self.hip    search_knn_self: the direct kernel over the tree's own records, the staged route's two kernels
 // Everything here is `inline` (or a type): every unit sees the same definitions, the linker keeps one.
 #pragma once
 
@@ -634,6 +635,18 @@ inline int check_knn_within(const Tree* t, const void* q, uint64_t nq, uint32_t 
   if (rc != PTK_OK || nq == 0) return rc;
   if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
   if (topological(t)) return fail(PTK_ERR_UNSUPPORTED, "search_knn_within: topological metrics run on the host loop only");
+  return PTK_OK;
+}
+// search_knn_self (ptk.h): no query buffer -- the rows are the tree's own points.  (The handle checks of check_search,
+// spelled with the tree's points as the batch: a tree holds at least one point.)
+template <class Tree>
+inline int check_knn_self(const Tree* t, uint32_t k, const void* out) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  int rc = check_search(t, t, t->n_points);
+  if (rc == PTK_OK) rc = check_k(k);
+  if (rc != PTK_OK) return rc;
+  if (k == 0xFFFFFFFFu) return fail(PTK_ERR_INVALID, "k + 1 does not fit 32 bits");  // (the search runs with k + 1)
+  if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
   return PTK_OK;
 }
 template <class Tree>

@@ -1008,6 +1008,42 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
   return rc;
 }
 
+// search_knn_self (ptk.h): every float64 tree takes the staged route -- the tree's points, piece by piece
+// in leaf order, through the search above with k + 1, and the rule of the contract on its rows.
+int ptk_search64_knn_self_device(const ptk_tree64* t, uint32_t k, ptk_neighbor64* d_out, void* stream) {
+  const int rc = check_knn_self(t, k, d_out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  return ptkf::self_staged<double, ptk_neighbor64>(
+      t->n_points, t->dim, k, s,
+      [&](uint64_t first, uint64_t n, double* d_q) {
+        return ptkf::self_queries64(t->dev.pts, t->dev.stride, t->dim, first, n, d_q, s);
+      },
+      [&](const double* d_q, uint64_t n, ptk_neighbor64* d_rows) { return ptk_search64_knn_device(t, d_q, n, k + 1u, 1.0, d_rows, s); },
+      [&](const ptk_neighbor64* d_rows, uint64_t first, uint64_t n) {
+        return ptkf::drop_self64(d_rows, t->dev.index, first, n, k, d_out, s);
+      });
+}
+
+int ptk_search64_knn_self(const ptk_tree64* t, uint32_t k, ptk_neighbor64* out) {
+  const int rc = check_knn_self(t, k, out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bo;  // (nothing goes up: the rows come down only)
+  const size_t out_bytes = (size_t)t->n_points * k * sizeof(ptk_neighbor64);
+  hipError_t he = bo.get(t, 1, out_bytes);
+  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (%zu bytes of rows): %s", out_bytes, hipGetErrorString(he));
+  const int src = ptk_search64_knn_self_device(t, k, reinterpret_cast<ptk_neighbor64*>(bo.p), nullptr);
+  if (src != PTK_OK) return src;
+  he = hipMemcpy(out, bo.p, out_bytes, hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  return PTK_OK;
+}
+
 // search_knn_within (ptk.h).  The list starts at radius * (1 + 2^-10) (as the float32 search); DBL_MAX
 // -- the plain search, masked at store -- for metric_lpinf / metric_lninf, trees deeper than the margin covers
 // (~2 000 levels), a radius that is subnormal or whose margin overflows.

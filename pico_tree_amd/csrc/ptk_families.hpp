@@ -126,4 +126,55 @@ int count64_within_radii(const ptk::DevTree64& dev, int metric, const ptk::Count
 void warm_count();
 // ptk_family_f64.hip
 void warm_f64();
+// ptk_family_self.hip: search_knn_self.  knn_self: the direct kernel on leaf positions [first, first + n)
+// of a float32 tree with dim <= 3, a non-topological metric, a private stack class and k + 1 <= 64 (self_direct below).
+// The staged route's two kernels take plain pointers, so that either precision's entry points can call them:
+// self_queries* writes the positions' points as dim-wide rows (`recs`: the 16-byte records, else `pts` with `stride`
+// scalars per point), drop_self* applies the rule to rows of k + 1 records and writes row `self` of the output.
+int knn_self(const ptk_tree* t, uint64_t first, uint64_t n, uint32_t k, ptk::Neighbor* d_out, hipStream_t s);
+int self_queries(const float4* recs, const float* pts, uint32_t stride, uint32_t dim, uint64_t first, uint64_t n, float* d_q,
+                 hipStream_t s);
+int self_queries64(const double* pts, uint32_t stride, uint32_t dim, uint64_t first, uint64_t n, double* d_q, hipStream_t s);
+int drop_self(const ptk::Neighbor* rows, const float4* recs, const int32_t* index, uint64_t first, uint64_t n, uint32_t k,
+              ptk::Neighbor* d_out, hipStream_t s);
+int drop_self64(const void* rows, const int32_t* index, uint64_t first, uint64_t n, uint32_t k, void* d_out, hipStream_t s);
+void warm_self();
+// Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
+// kSelfStageBytes; test hook self_piece.
+constexpr size_t kSelfStageBytes = size_t(256) << 20;
+inline uint64_t self_piece_rows(uint32_t dim, uint32_t k, size_t scalar_bytes, size_t record_bytes) {
+  const int forced = ptkb::knob_int("self_piece", 0);
+  if (forced > 0) return (uint64_t)forced;
+  const size_t per_row = (size_t)dim * scalar_bytes + ((size_t)k + 1) * record_bytes;
+  return std::max<uint64_t>(64, kSelfStageBytes / per_row);
+}
+// The staged route over either handle: per piece of leaf positions, the three steps of DESIGN.md §2.  `queries(first, n,
+// d_q)`, `search(d_q, n, d_rows)` -- the handle's own device search with k + 1, which takes the handle's scratch lock
+// itself -- and `drop(d_rows, first, n)` enqueue on the caller's stream; the temporaries are one per-call block, freed
+// after a wait for the stream (this route allocates and waits: it is not enqueue-only, ptk.h).
+template <class Real, class Nb, class Queries, class Search, class Drop>
+inline int self_staged(uint64_t n_points, uint32_t dim, uint32_t k, hipStream_t s, Queries&& queries, Search&& search,
+                       Drop&& drop) {
+  const uint64_t max_batch = (uint64_t)std::max(1, ptkb::env_int("PTK_MAX_BATCH", 1 << 25));
+  const uint64_t piece = std::min(std::min(self_piece_rows(dim, k, sizeof(Real), sizeof(Nb)), max_batch), n_points);
+  const size_t q_bytes = ((size_t)piece * dim * sizeof(Real) + 255) & ~(size_t)255;
+  ptkb::DeviceBlock block;
+  if (block.alloc(q_bytes + (size_t)piece * ((size_t)k + 1) * sizeof(Nb)) != hipSuccess) {
+    (void)hipGetLastError();
+    return ptkb::fail(PTK_ERR_NOMEM, "out of device memory (the temporaries of search_knn_self)");
+  }
+  Real* d_q = block.as<Real>();
+  Nb* d_rows = reinterpret_cast<Nb*>(block.as<char>() + q_bytes);
+  int rc = PTK_OK;
+  for (uint64_t first = 0; first < n_points && rc == PTK_OK; first += piece) {
+    const uint64_t n = std::min(piece, n_points - first);
+    rc = queries(first, n, d_q);
+    if (rc == PTK_OK) rc = search(d_q, n, d_rows);
+    if (rc == PTK_OK) rc = drop(d_rows, first, n);
+  }
+  // (the block is freed when this returns: everything enqueued on it has to be done -- also after a refusal half-way)
+  if (hipStreamSynchronize(s) != hipSuccess && rc == PTK_OK)
+    rc = ptkb::fail(PTK_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
 }  // namespace ptkf

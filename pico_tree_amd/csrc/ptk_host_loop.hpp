@@ -267,6 +267,48 @@ int ptk_host_search_knn(const ptk_tree* t, const float* points, const float* q, 
   return PTK_OK;
 }
 
+// search_knn_self (ptk.h) as it is written: the reference's search_knn row of m = min(k + 1, n_points) entries for each
+// tree point, the entry the rule names removed (the first whose index is the row's, else the last), the row padded
+// with {-1, FLT_MAX}.
+int ptk_host_search_knn_self(const ptk_tree* t, const float* points, uint32_t k, ptk_neighbor* out) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    auto* rows = reinterpret_cast<neighbor_t*>(out);
+    const uint32_t m = (uint32_t)std::min<uint64_t>((uint64_t)k + 1, t->n_points);
+    const float fmax = std::numeric_limits<float>::max();
+    rows_loop(t->n_points, [&](uint64_t i) {
+      std::vector<neighbor_t> full(m);
+      internal::knn_visitor<neighbor_t*> v(full.data(), full.data() + m);
+      search_one(t, flat, view, points + i * t->dim, v);
+      const uint32_t found = (uint32_t)(v.filled() - full.data());  // (only what the search wrote)
+      uint32_t drop = m - 1;
+      for (uint32_t j = 0; j < found; ++j)
+        if (full[j].index == (int)i) {
+          drop = j;
+          break;
+        }
+      neighbor_t* b = rows + i * k;
+      uint32_t n = 0;
+      for (uint32_t j = 0; j < found; ++j)
+        if (j != drop && full[j].distance < fmax) b[n++] = full[j];
+      for (; n < k; ++n) b[n] = neighbor_t{-1, fmax};
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 int ptk_host_search_knn_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, uint32_t k,
                                float radius, ptk_neighbor* out) {
   if (t == nullptr || points == nullptr || (nq > 0 && (q == nullptr || out == nullptr)))

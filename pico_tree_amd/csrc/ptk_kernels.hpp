@@ -1517,6 +1517,112 @@ __global__ __launch_bounds__(BLOCK) PTK_KNN_REG_WAVES void knn_reg_within_radii_
   pol.store(out + qi * k);
 }
 
+// ---- search_knn_self: each tree point's k nearest OTHER points -----------------
+// The rule of the contract on one row of k + 1 records, read through get(j): the entry that leaves is the first accepted
+// one whose index is `self`, else the last; the other k keep their order; a slot the search never accepted (its distance
+// is at the sentinel `fmax`) is the pad {-1, fmax}.  One statement of it for the direct kernel and the staged route.
+template <class Nb, class Real, class Get>
+__host__ __device__ __forceinline__ void drop_self_row(Get&& get, uint32_t k, int32_t self, Real fmax, Nb* __restrict__ row) {
+  uint32_t drop = k;
+  for (uint32_t j = 0; j < k; ++j) {
+    const Nb nb = get(j);
+    if (drop == k && nb.index == self && nb.distance < fmax) drop = j;
+  }
+  for (uint32_t j = 0; j < k; ++j) {
+    Nb nb = get(j < drop ? j : j + 1u);
+    if (!(nb.distance < fmax)) {
+      nb.index = -1;
+      nb.distance = fmax;
+    }
+    if constexpr (sizeof(Nb) == 16) nb.pad_ = 0;  // (the float64 record's padding word)
+    row[j] = nb;
+  }
+}
+
+// K17.  knn_reg_kernel over the tree's own points: lane j of the launch is leaf-order record first + j of DevTree::pts --
+// one aligned 16-byte load per lane, a wavefront reads 1 KB contiguous; no query buffer, no permutation, no scratch.  The
+// list is the register list of k + 1 entries knn_reg_kernel would produce for that row; the rule above is applied to it
+// in registers as it leaves (slot j of the row is list slot j, or j + 1 from the dropped entry on).  `k`: the caller's k,
+// K >= k + 1.  Never capped.
+template <int K, int S, int OVF, int BLOCK, int LEAFB, class M = MetricL2>
+__global__ __launch_bounds__(BLOCK) PTK_KNN_REG_WAVES void knn_self_kernel(
+    DevTree t, uint32_t dim, uint64_t first, uint64_t n, uint32_t k, Neighbor* __restrict__ out) {
+  const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
+  const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const float4 rec = t.pts[first + i];
+  PTK_KEEP4(rec);
+  const float qx = rec.x;
+  float qy = rec.y, qz = rec.z;
+  const int32_t self = (int32_t)__float_as_uint(rec.w);
+  pad_query<M>(dim, qy, qz);
+  Record spill[OVF > 0 ? OVF : 1];
+  Stack<S, OVF, BLOCK> st;
+  st.init((LdsWord*)ptk_smem, threadIdx.x, spill);
+  KnnRegPolicy<K> pol;
+  pol.init(k + 1u, 1.0f);
+  traverse<LEAFB, false, M>(t, qx, qy, qz, pol, st);
+  // The k + 1 entries are slots K - 1 - k .. K - 1.  `drop`: the slot that leaves (K - 1, the last, unless an earlier
+  // accepted one is the lane's own point).
+  const uint32_t lo = (uint32_t)K - 1u - k;
+  uint32_t drop = (uint32_t)K - 1u;
+#pragma unroll
+  for (int j = K - 1; j >= 0; --j) {
+    if ((uint32_t)j >= lo && pol.li[j] == self && pol.ld[j] < 3.402823466e+38f) drop = (uint32_t)j;
+  }
+  Neighbor* __restrict__ row = out + (uint64_t)(uint32_t)self * k;
+#pragma unroll
+  for (int j = 0; j < K - 1; ++j) {
+    if ((uint32_t)j >= lo) {
+      const bool shift = (uint32_t)j >= drop;
+      Neighbor nb;
+      nb.index = shift ? pol.li[j + 1] : pol.li[j];
+      nb.distance = shift ? pol.ld[j + 1] : pol.ld[j];
+      if (!(nb.distance < 3.402823466e+38f)) {
+        nb.index = -1;
+        nb.distance = 3.402823466e+38f;
+      }
+      row[(uint32_t)j - lo] = nb;
+    }
+  }
+}
+
+// The staged route (every handle the direct kernel does not serve).  Step 1: leaf positions [first, first + n) as
+// dim-wide query rows.  `recs`: the 16-byte records of a float32 tree with dim <= 3; otherwise `pts` holds `stride`
+// scalars per point, the first dim of them its coordinates (the row-major points of dim > 3, the records of float64).
+template <class Real>
+__global__ __launch_bounds__(256) void self_queries_kernel(
+    const float4* __restrict__ recs, const Real* __restrict__ pts, uint32_t stride, uint32_t dim, uint64_t first, uint64_t n,
+    Real* __restrict__ q) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  if constexpr (sizeof(Real) == 4) {
+    if (recs != nullptr) {
+      const float4 rec = recs[first + i];
+      PTK_KEEP4(rec);
+      q[i * dim] = rec.x;
+      if (dim > 1) q[i * dim + 1] = rec.y;
+      if (dim > 2) q[i * dim + 2] = rec.z;
+      return;
+    }
+  }
+  const Real* __restrict__ p = pts + (first + i) * stride;
+  for (uint32_t a = 0; a < dim; ++a) q[i * dim + a] = p[a];
+}
+
+// Step 3: the rule of the contract on row i of `rows` (k + 1 records, the search's), one lane per row; the row's point is
+// leaf position first + i, its index the record's fourth word or index[first + i].
+template <class Nb, class Real>
+__global__ __launch_bounds__(256) void drop_self_kernel(
+    const Nb* __restrict__ rows, const float4* __restrict__ recs, const int32_t* __restrict__ index, uint64_t first,
+    uint64_t n, uint32_t k, Real fmax, Nb* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const int32_t self = recs != nullptr ? (int32_t)__float_as_uint(recs[first + i].w) : index[first + i];
+  const Nb* __restrict__ src = rows + i * ((uint64_t)k + 1u);
+  drop_self_row<Nb, Real>([&](uint32_t j) { return src[j]; }, k, self, fmax, out + (uint64_t)(uint32_t)self * k);
+}
+
 // ---- radius: count pass and fill pass ------------------------------------------------------
 // n_dev (fill pass only): the batch is the first *n_dev entries of perm -- the rows a capture
 // could not hold, listed on the device (no host round trip to size the launch).
