@@ -210,6 +210,13 @@ struct ptk_api<float> {
     return ptk_search_knn_within(t, q, nq, k, r, out);
   }
   static int knn_self(tree const* t, std::uint32_t k, neighbor* out) { return ptk_search_knn_self(t, k, out); }
+  // (radii null: every point gets `radius`; else one radius per tree point, by original index)
+  static int count_within_self(tree const* t, float radius, float const* radii, std::uint64_t max_count, std::uint64_t* counts) {
+    return ptk_search_count_within_self(t, radius, radii, max_count, counts);
+  }
+  static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
+    return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
+  }
   static int count_within(tree const* t, float const* q, std::uint64_t nq, float r, std::uint64_t max_count,
                           std::uint64_t* counts) {
     return ptk_search_count_within(t, q, nq, r, max_count, counts);
@@ -248,6 +255,12 @@ struct ptk_api<double> {
     return ptk_search64_knn_within(t, q, nq, k, r, out);
   }
   static int knn_self(tree const* t, std::uint32_t k, neighbor* out) { return ptk_search64_knn_self(t, k, out); }
+  static int count_within_self(tree const* t, double radius, double const* radii, std::uint64_t max_count, std::uint64_t* counts) {
+    return ptk_search64_count_within_self(t, radius, radii, max_count, counts);
+  }
+  static int radius_self(tree const* t, double radius, double const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
+    return ptk_search64_radius_self(t, radius, radii, sort, offsets, out);
+  }
   static int count_within(tree const* t, double const* q, std::uint64_t nq, double r, std::uint64_t max_count,
                           std::uint64_t* counts) {
     return ptk_search64_count_within(t, q, nq, r, max_count, counts);

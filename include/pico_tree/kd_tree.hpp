@@ -288,6 +288,30 @@ class kd_tree {
     if (sort) v.sort();
   }
 
+  //! The neighbours of the tree's own point \p index within \p radius among the
+  //! OTHER points: the search_radius row of that point without
+  //! the entry whose index is \p index, if there is one; the other entries keep
+  //! their order (traversal order, ascending distance with \p sort).
+  inline void search_radius_self(
+      index_type const index,
+      scalar_type const radius,
+      std::vector<neighbor_type>& n,
+      bool const sort = false) const {
+    auto const points = view();
+    if (index < index_type(0) || static_cast<size_type>(index) >= points.size()) {
+      throw std::out_of_range("pico_tree: search_radius_self: no such point");
+    }
+    n.clear();
+    auto const x = make_row(points[index], points.sdim());
+    search_radius(x, radius, n, sort);
+    for (size_type j = 0; j < n.size(); ++j) {
+      if (n[j].index == index) {
+        n.erase(n.begin() + static_cast<std::ptrdiff_t>(j));
+        break;
+      }
+    }
+  }
+
   //! All indices inside the closed box [min, max].
   template <typename P_>
   inline void search_box(
@@ -359,6 +383,38 @@ class kd_tree {
   //! on failure; k == 0 is std::invalid_argument.
   inline void search_knn_self(size_type const k, std::vector<neighbor_type>& out) const {
     batched_knn_self(k, out);
+  }
+
+  //! Every point's neighbours within \p radius among the other points:
+  //! rows[i] = search_radius_self(i, radius, ..., sort); rows is resized to
+  //! size().  There is no query space: the backend holds the points.  Served
+  //! by the backend (ptk_search_radius_self); where it refuses (and
+  //! allow_host_loop is on), and in a build with PICO_TREE_HOST_ONLY defined,
+  //! by a loop over the per-point member.  \p radius must be >= 0 and not NaN.
+  inline void search_radius_self(
+      scalar_type const radius, std::vector<std::vector<neighbor_type>>& rows, bool const sort = false) const {
+    batched_radius_self(radius, nullptr, rows, sort);
+  }
+
+  //! ... with one radius per tree point, by original index; radii.size() must
+  //! be size() (std::invalid_argument otherwise), every entry >= 0 and not NaN.
+  inline void search_radius_self(
+      std::vector<scalar_type> const& radii, std::vector<std::vector<neighbor_type>>& rows, bool const sort = false) const {
+    check_radii(radii, view().size());
+    batched_radius_self(scalar_type(0), radii.data(), rows, sort);
+  }
+
+  //! counts[i] = the length of row i of search_radius_self, clamped to
+  //! \p max_count when that is > 0 (after the point itself has left); counts
+  //! must hold size() entries.
+  inline void count_within_self(scalar_type const radius, size_type* counts, size_type const max_count = 0) const {
+    batched_count_within_self(radius, nullptr, counts, max_count);
+  }
+
+  inline void count_within_self(
+      std::vector<scalar_type> const& radii, size_type* counts, size_type const max_count = 0) const {
+    check_radii(radii, view().size());
+    batched_count_within_self(scalar_type(0), radii.data(), counts, max_count);
   }
 
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
@@ -713,6 +769,67 @@ class kd_tree {
       internal::ptk_check(
           api::knn_self(device(), static_cast<std::uint32_t>(k), reinterpret_cast<typename api::neighbor*>(out.data())),
           "ptk_search_knn_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  // (radii null: every point gets `radius`)
+  void batched_radius_self(
+      scalar_type radius, scalar_type const* radii, std::vector<std::vector<neighbor_type>>& rows, bool sort) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    size_type const n = view().size();
+    auto const rows_loop = [&]() {
+      rows.assign(n, std::vector<neighbor_type>());
+      internal::host_rows_loop(n, [&](size_type i) {
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, rows[i], sort);
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    std::vector<std::uint64_t> offsets(n + 1, 0);
+    typename api::neighbor* flat = nullptr;
+    try {
+      internal::ptk_check(
+          api::radius_self(device(), radius, radii, sort ? 1 : 0, offsets.data(), &flat), "ptk_search_radius_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+      return;
+    }
+    library_rows keep(flat);  // freed even if the copy below throws
+    auto const* src = reinterpret_cast<neighbor_type const*>(flat);
+    rows.resize(n);
+    for (size_type i = 0; i < n; ++i) rows[i].assign(src + offsets[i], src + offsets[i + 1]);
+#endif
+  }
+
+  void batched_count_within_self(
+      scalar_type radius, scalar_type const* radii, size_type* counts, size_type max_count) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    size_type const n = view().size();
+    auto const rows_loop = [&]() {
+      internal::host_rows_loop(n, [&](size_type i) {
+        std::vector<neighbor_type> row;
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, row);
+        counts[i] = max_count != 0 && row.size() > max_count ? max_count : row.size();
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    std::vector<std::uint64_t> c(n);
+    try {
+      internal::ptk_check(
+          api::count_within_self(device(), radius, radii, static_cast<std::uint64_t>(max_count), c.data()),
+          "ptk_search_count_within_self");
+      std::copy(c.begin(), c.end(), counts);
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

@@ -405,6 +405,49 @@ int ptk_search_radius_radii_fill_device(const ptk_tree* tree, const float* d_que
 int ptk_search_radius_radii(const ptk_tree* tree, const float* queries, uint64_t nq, const float* radii, int sort,
                             uint64_t* offsets, ptk_neighbor** out);
 
+/* ---- the radius searches of the tree's own points ------------------------- */
+
+/* The fixed-radius counterpart of ptk_search_knn_self: every tree point's neighbours among the OTHER points, with no
+ * query buffer (radius outlier removal, DBSCAN core-point tests, density estimates, normals over a metric
+ * neighbourhood).  Results contract.  Let R_i be the reference's search_radius(p_i, r_i) row on the
+ * handle's tree and points: exact (no e), the handle's metric, strict acceptance (distance < r_i); r_i is `radius`, or
+ * radii[i] when `radii` is not NULL (n_points entries, indexed by ORIGINAL point index; `radius` is then ignored).
+ *   Rows.  Row i is R_i with the entry whose index is i removed if there is one (an index occurs at most once in a
+ * row); the other entries keep the reference's traversal order, the same indices and distance bits; with sort != 0
+ * they ascend by distance (ties: unspecified order for float32, by index for float64).  Coincident OTHER points stay in
+ * the row at distance 0.  Neither "drop the first entry" (the own point is usually not first: rows are in traversal
+ * order) nor "the count minus one" (on a tree read from a stream that does not belong to its points a point is often
+ * absent from its own row) is this function.
+ *   Counts.  counts[i] is the length of row i; with max_count > 0, min(that length, max_count): the clamp applies
+ * AFTER the own entry has left.
+ *   Ordering.  Rows and counts are indexed by original point index: n_points rows, offsets has n_points + 1 entries.
+ *   Radius values.  0 gives empty rows; +inf, FLT_MAX / DBL_MAX and subnormal radii are valid.  A NaN or negative scalar
+ * radius is PTK_ERR_INVALID.  A NaN or negative radii entry is PTK_ERR_INVALID in the host-buffer forms and the host
+ * loops (the message names the first such row); in the _device forms such a row is empty -- count 0, the fill writes
+ * nothing for it -- and every other row is unaffected.
+ *   Non-finite points (a handle read from a stream may hold some): such a point's row is whatever the reference gives
+ * it, and it changes no other row.
+ *   State.  The handle's radius capture (ptk_search_radius_count_device / _fill_device) is neither read nor
+ * invalidated.  The first call builds the handle's count side table if it has none, as ptk_search_count_within does.
+ * Where the device serves them: exactly the handles ptk_search_count_within_radii serves -- dim <= 3, the four
+ * non-topological metrics, float32 trees not of the deep stack class, float64 trees of any depth.  Every other handle
+ * is PTK_ERR_UNSUPPORTED; the message names the reason and the host loop that serves it (ptk_host_search_count_within_self
+ * / ptk_host_search_radius_self: every float32 handle, the topological metrics included).  There is no staged route.
+ * A null output with n_points > 0 is PTK_ERR_INVALID, a host-only handle PTK_ERR_DEVICE.
+ * The _device forms only enqueue on `stream`: they allocate nothing and do not wait, except for the first build of the
+ * side table.  The count pass that belongs to ptk_search_radius_self_fill_device is ptk_search_count_within_self_device
+ * with max_count = 0: the caller scans its counts into d_offsets (n_points + 1 entries, exclusive) and calls the fill
+ * with the same radius / d_radii on the same stream.  ptk_search_radius_self: offsets (n_points + 1, host) is filled,
+ * *out is malloc'ed by the library (free with ptk_free). */
+int ptk_search_count_within_self(const ptk_tree* tree, float radius, const float* radii, uint64_t max_count,
+                                 uint64_t* counts);
+int ptk_search_count_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, uint64_t max_count,
+                                        uint64_t* d_counts, void* stream);
+int ptk_search_radius_self(const ptk_tree* tree, float radius, const float* radii, int sort, uint64_t* offsets,
+                           ptk_neighbor** out);
+int ptk_search_radius_self_fill_device(const ptk_tree* tree, float radius, const float* d_radii, const uint64_t* d_offsets,
+                                       ptk_neighbor* d_out, int sort, void* stream);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -451,6 +494,13 @@ int ptk_host_search_radius(const ptk_tree* tree, const float* points, const floa
 /* (the loop above with the row's own radius and e = 1: radii as for the other ptk_host_*_radii loops) */
 int ptk_host_search_radius_radii(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq,
                                  const float* radii, int sort, uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
+/* (ptk_search_count_within_self / ptk_search_radius_self as they are written: the radius search of each of the tree's
+ * own points -- `points`, n_points rows --, then the removal of the own entry; every metric, the topological ones
+ * included; radii NULL: every point gets `radius`) */
+int ptk_host_search_count_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
+                                      uint64_t max_count, uint64_t* counts);
+int ptk_host_search_radius_self(const ptk_tree* tree, const float* points, float radius, const float* radii, int sort,
+                                uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 
@@ -556,6 +606,14 @@ int ptk_search64_radius(const ptk_tree64* tree, const double* queries,
 /* As ptk_search_radius_radii: radii in double; served where ptk_search64_count_within_radii is. */
 int ptk_search64_radius_radii(const ptk_tree64* tree, const double* queries, uint64_t nq, const double* radii, int sort,
                               uint64_t* offsets, ptk_neighbor64** out);
+/* As ptk_search_count_within_self / _device and ptk_search_radius_self: radii in double, ptk_neighbor64 records.  (The
+ * _device form takes the handle's stack block, which grows on first use.) */
+int ptk_search64_count_within_self(const ptk_tree64* tree, double radius, const double* radii, uint64_t max_count,
+                                   uint64_t* counts);
+int ptk_search64_count_within_self_device(const ptk_tree64* tree, double radius, const double* d_radii, uint64_t max_count,
+                                          uint64_t* d_counts, void* stream);
+int ptk_search64_radius_self(const ptk_tree64* tree, double radius, const double* radii, int sort, uint64_t* offsets,
+                             ptk_neighbor64** out);
 /* As ptk_search_box. */
 int ptk_search64_box(const ptk_tree64* tree, const double* mins,
                      const double* maxs, uint64_t nb, uint64_t* offsets,

@@ -98,6 +98,10 @@ _SIGNATURES = {
                                       c_void_p]),
     "ptk_search_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
     "ptk_search_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
+    "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
+    "ptk_search_radius_self_fill_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "ptk_search_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_search_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p, c_void_p]),
     "ptk_search_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -125,6 +129,8 @@ _SIGNATURES = {
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_self": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
+    "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
     "ptk_host_search_knn_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p]),
     "ptk_host_search_count_within_radii": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
@@ -150,6 +156,9 @@ _SIGNATURES = {
     "ptk_search64_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
     "ptk_search64_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "ptk_search64_count_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p]),
+    "ptk_search64_count_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_radius_self": (c_int, [c_void_p, c_double, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_search64_knn_within": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p]),
     "ptk_search64_knn_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_count_within": (c_int, [c_void_p, c_void_p, c_uint64, c_double, c_uint64, c_void_p]),
@@ -1035,6 +1044,103 @@ class KdTree:
                      lambda lib: lib.ptk_host_search_count_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq,
                                                                   np.float32(radius), max_count, counts.ctypes.data))
         return counts
+
+    def _self_radii(self, radius, device: bool):
+        """(scalar, radii) of a self search: one radius (radii None), or one per tree point by original index -- a host
+        array of the tree's dtype, or with ``device`` a contiguous CUDA tensor on the tree's device (a host array-like
+        is checked for NaN / negative entries here and uploaded)."""
+        if _is_scalar_radius(radius):
+            return self._real(radius), None
+        n = self._npts
+        if not device:
+            return self._real(0), self._host_radii(radius, n)
+        import torch
+        dev = torch.device("cuda", int(self.info()["device"]))
+        if not (_is_torch(radius) and radius.is_cuda):
+            host = self._host_radii(radius, n)
+            bad = np.flatnonzero(~(host >= 0))
+            if len(bad):
+                raise ValueError(f"radius[{int(bad[0])}] must be >= 0 (and not NaN)")
+            return self._real(0), torch.from_numpy(host).to(dev)
+        tq = torch.float64 if self._f64 else torch.float32
+        if radius.device != dev:
+            raise ValueError(f"radius must be on the tree's device ({dev}), not on {radius.device}")
+        if radius.dtype != tq:
+            raise ValueError(f"radius must be a {self._dtype.name} tensor, not {radius.dtype}")
+        if radius.dim() != 1 or radius.shape[0] != n:
+            raise ValueError(f"radius must be a scalar or a 1-D tensor of {n} radii, one per tree point")
+        if not radius.is_contiguous():
+            raise ValueError("radius must be a contiguous tensor")
+        return self._real(0), radius
+
+    def count_within_self(self, radius, max_count: int = 0, device: bool = False):
+        """``count_within_self(radius, max_count=0, device=False)`` -- how many OTHER tree points lie closer than
+        ``radius`` to each tree point.
+
+        ``counts[i]`` is the length of :meth:`search_radius_self`'s row i, clamped to ``max_count`` when that is > 0
+        (the clamp applies after the point itself has left).  ``radius`` is a scalar or an array of ``npts`` radii
+        indexed by original point index.  No query array: the tree holds its points on the device
+        (``ptk_search_count_within_self`` / ``ptk_search64_count_within_self``).  Returns an ``int64[npts]`` array;
+        with ``device=True`` an ``int64`` CUDA tensor on the tree's device, enqueued on the current torch stream (a
+        CUDA tensor of radii is taken as it is: a NaN or negative entry gives count 0).  Served where
+        :meth:`count_within` with an array is; the rest is refused (``allow_host_loop`` serves float32 trees)."""
+        max_count = int(max_count)
+        if max_count < 0:
+            raise ValueError("max_count must be >= 0")
+        r, radii = self._self_radii(radius, device)
+        n = self._npts
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            out = torch.empty((n,), dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(self._fn("ptk_search_count_within_self_device")(
+                self._h, r, radii.data_ptr() if radii is not None else None, max_count, out.data_ptr(), stream))
+            return out
+        counts = np.zeros((n,), dtype=np.int64)
+        rp = radii.ctypes.data if radii is not None else None
+        self._served(self._fn("ptk_search_count_within_self")(self._h, r, rp, max_count, counts.ctypes.data),
+                     lambda lib: lib.ptk_host_search_count_within_self(self._h, self._pts.ctypes.data, r, rp, max_count,
+                                                                       counts.ctypes.data))
+        return counts
+
+    def search_radius_self(self, radius, sort: bool = False, device: bool = False):
+        """``search_radius_self(radius, sort=False, device=False)`` -- each tree point's neighbours within ``radius``
+        among the OTHER points of the tree.
+
+        Row i is :meth:`search_radius`'s row for point i (exact, strict ``distance < radius``) without the entry whose
+        index is i, if there is one; the other entries keep their order (traversal order, or ascending distance with
+        ``sort``); coincident other points stay at distance 0.  ``radius`` is a scalar or an array of ``npts`` radii
+        indexed by original point index; a NaN or negative value is refused (by its row).  No query array
+        (``ptk_search_radius_self`` / ``ptk_search64_radius_self``).  Returns a :class:`DArray`; with ``device=True``
+        (float32 trees) ``(offsets int64 tensor [npts + 1], raw int32 tensor [total, 2])`` on the current torch stream,
+        as :meth:`search_radius_device` (a NaN or negative entry of a CUDA tensor of radii gives an empty row).  Served
+        where :meth:`count_within_self` is."""
+        r, radii = self._self_radii(radius, device)
+        n = self._npts
+        lib = _load()
+        if device:
+            import torch
+            self._float32_only("search_radius_self(device=True)")
+            dev = torch.device("cuda", int(self.info()["device"]))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rp = radii.data_ptr() if radii is not None else None
+            counts = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            _check(lib.ptk_search_count_within_self_device(self._h, r, rp, 0, counts.data_ptr(), stream))
+            offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            offsets[1:] = torch.cumsum(counts[:n], 0)
+            total = int(offsets[-1].item())
+            out = torch.empty((max(total, 1), 2), dtype=torch.int32, device=dev)
+            _check(lib.ptk_search_radius_self_fill_device(self._h, r, rp, offsets.data_ptr(), out.data_ptr(),
+                                                          int(bool(sort)), stream))
+            return offsets, out[:total]
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        rows = c_void_p()
+        rp = radii.ctypes.data if radii is not None else None
+        self._served(self._fn("ptk_search_radius_self")(self._h, r, rp, int(bool(sort)), offsets.ctypes.data, byref(rows)),
+                     lambda lib: lib.ptk_host_search_radius_self(self._h, self._pts.ctypes.data, r, rp, int(bool(sort)),
+                                                                 offsets.ctypes.data, byref(rows)))
+        return DArray(offsets, _adopt(lib, rows, int(offsets[-1]), self._neighbor))
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

@@ -2395,6 +2395,129 @@ int ptk_search_radius_radii(const ptk_tree* t, const float* q, uint64_t nq, cons
   return rc;
 }
 
+// ---- the radius searches of the tree's own points (ptk.h) -----------------------
+
+// count_within_self: count_self_kernel over ranges of leaf positions (the piece rule of ptk_search_knn_self) -- no
+// scratch, nothing allocated but the handle's count side table on its first use, nothing waited for.  The handle's
+// radius capture is neither read nor invalidated.
+int ptk_search_count_within_self_device(const ptk_tree* t, float radius, const float* d_radii, uint64_t max_count,
+                                        uint64_t* d_counts, void* stream) {
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_counts, "count_within_self",
+                             "ptk_host_search_count_within_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = count_table_of(t, s);
+  if (rc != PTK_OK) return rc;
+  const bool shortcut = knob_int("count_shortcut", 1) != 0;
+  return in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+    return ptkf::count_self(t, first, n, radius, d_radii, max_count, shortcut, d_counts, s);
+  });
+}
+
+// The fill pass behind ptk_search_count_within_self_device(max_count = 0) and a scan of its counts.
+int ptk_search_radius_self_fill_device(const ptk_tree* t, float radius, const float* d_radii, const uint64_t* d_offsets,
+                                       ptk_neighbor* d_out, int sort, void* stream) {
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_offsets, "search_radius_self",
+                             "ptk_host_search_radius_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  auto* o = reinterpret_cast<ptk::Neighbor*>(d_out);
+  rc = in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+    return ptkf::radius_self_fill(t, first, n, radius, d_radii, d_offsets, o, s);
+  });
+  if (rc == PTK_OK && sort) {
+    Timer timer(t, s);
+    const uint32_t blocks = (uint32_t)((t->n_points + ptk::kBlock - 1) / ptk::kBlock);
+    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, t->n_points, d_offsets, o);
+    PTK_HIP(hipGetLastError());
+    timer.stop(2, 0);
+  }
+  return rc;
+}
+
+// The host form: only the radii go up (behind nothing: there are no queries), the counts come down.
+int ptk_search_count_within_self(const ptk_tree* t, float radius, const float* radii, uint64_t max_count, uint64_t* counts) {
+  const int rc = check_radius_self(t, radius, radii, /*host_values=*/true, counts, "count_within_self",
+                                   "ptk_host_search_count_within_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t out_bytes = (size_t)t->n_points * sizeof(uint64_t);
+  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
+  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
+  if (src != PTK_OK) return src;
+  const float* d_radii = nullptr;
+  if (radii != nullptr) {
+    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
+    d_radii = reinterpret_cast<const float*>(io.d_in);
+  }
+  src = ptk_search_count_within_self_device(t, radius, d_radii, max_count, reinterpret_cast<uint64_t*>(io.d_out), io.search[0]);
+  if (src != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return src;
+  }
+  PTK_HIP(hipMemcpyAsync(counts, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  return PTK_OK;
+}
+
+// Convenience, as ptk_search_radius_radii: the count, the scan and the fill on the device.
+int ptk_search_radius_self(const ptk_tree* t, float radius, const float* radii, int sort, uint64_t* offsets,
+                           ptk_neighbor** out) {
+  if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
+  *out = nullptr;
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, offsets, "search_radius_self",
+                             "ptk_host_search_radius_self");
+  if (rc != PTK_OK) return rc;
+  offsets[0] = 0;
+  const uint64_t np = t->n_points;
+  if (np == 0) return PTK_OK;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  DeviceBlock d_r, d_c, d_o, d_out;
+  hipError_t he = d_c.alloc((np + 1) * 8);
+  if (he == hipSuccess) he = d_o.alloc((np + 1) * 8);
+  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (np + 1) * 8);
+  if (he == hipSuccess && radii != nullptr) he = d_r.alloc(np * sizeof(float));
+  if (he == hipSuccess && radii != nullptr) he = hipMemcpy(d_r.p, radii, np * sizeof(float), hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    const float* d_radii = radii != nullptr ? d_r.as<float>() : nullptr;
+    uint64_t total = 0;
+    rc = ptk_search_count_within_self_device(t, radius, d_radii, 0, d_c.as<uint64_t>(), nullptr);
+    if (rc == PTK_OK) {
+      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), np, offsets);
+      if (he == hipSuccess) {
+        total = offsets[np];
+        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
+      }
+      if (he == hipSuccess)
+        rc = ptk_search_radius_self_fill_device(t, radius, d_radii, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort, nullptr);
+      if (he == hipSuccess && rc == PTK_OK) {
+        *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
+        if (*out == nullptr) {
+          rc = fail(PTK_ERR_NOMEM, "out of memory");
+        } else if (total > 0) {
+          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
+        }
+      }
+    }
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  if (rc != PTK_OK && *out) {
+    std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 namespace {

@@ -8,7 +8,8 @@
 //   ptk_family_nd.hip      any dimension > 3
 //   ptk_family_topo.hip    topological metrics
 //   ptk_family_f64.hip     double precision (ptk_backend_f64.hpp)
-//   ptk_family_self.hip    search_knn_self: the direct kernel over the tree's own records, the staged route's two kernels
+//   ptk_family_self.hip    search_knn_self: the direct kernel over the tree's own records, the staged route's two kernels;
+//                          search_radius_self / count_within_self (ptk_kernels_selfr.hpp), float32 and float64
 // Everything here is `inline` (or a type): every unit sees the same definitions, the linker keeps one.
 #pragma once
 
@@ -713,6 +714,27 @@ inline int check_radius_radii(const Tree* t, const void* q, uint64_t nq, const R
   if (rc != PTK_OK) return rc;
   if (offsets == nullptr) return fail(PTK_ERR_INVALID, "null offsets buffer");
   return check_count_within_radii(t, q, nq, radii, offsets, /*host_values=*/false);  // (the values are scanned above)
+}
+
+// search_radius_self / count_within_self (ptk.h): no query buffer -- the rows are the tree's own points.  `radii` null:
+// the scalar `radius` (>= 0, not NaN); else n_points radii by original point index (`host_values`: scanned, as
+// check_radii).  `out`: the counts, or the fill pass's offsets.  Served exactly where count_within_radii is; every other
+// handle is refused with the reason and `host_loop`, the call that serves it.
+template <class Tree, class Real>
+inline int check_radius_self(const Tree* t, double radius, const Real* radii, bool host_values, const void* out,
+                             const char* what, const char* host_loop) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  int rc = check_search(t, t, t->n_points);
+  if (rc != PTK_OK) return rc;
+  rc = radii == nullptr ? check_radius(radius) : check_radii(radii, t->n_points, host_values);
+  if (rc != PTK_OK) return rc;
+  if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+  if (t->dim > 3) return fail(PTK_ERR_UNSUPPORTED, "%s: dim > 3 runs on the host loop only (%s)", what, host_loop);
+  if (topological(t))
+    return fail(PTK_ERR_UNSUPPORTED, "%s: topological metrics run on the host loop only (%s)", what, host_loop);
+  if (deep_stack_class(t))
+    return fail(PTK_ERR_UNSUPPORTED, "%s: tree depth %u runs on the host loop only (%s)", what, t->max_depth, host_loop);
+  return PTK_OK;
 }
 
 inline float inv_ratio(float e) { return 1.0f / e; }

@@ -1377,6 +1377,121 @@ int ptk_search64_radius_radii(const ptk_tree64* t, const double* q, uint64_t nq,
   return rc;
 }
 
+// ---- the radius searches of the tree's own points (ptk.h) ----
+// count_within_self in double: count64_self_kernel over pieces of leaf positions (the lease's piece: the record stacks of
+// a launch live in the handle's stack block).  No batch order: the leaf order is one.
+static int count64_self_pieces(const ptk_tree64* t, double radius, const double* d_radii, uint64_t max_count,
+                               uint64_t* d_counts, hipStream_t s, Stack64Lease& lease) {
+  const bool shortcut = knob_int("count_shortcut", 1) != 0;
+  int rc = PTK_OK;
+  for (uint64_t first = 0; first < t->n_points && rc == PTK_OK; first += lease.piece)
+    rc = ptkf::count64_self(t->dev, t->metric.load(), static_cast<const ptk::CountBox64*>(t->d_count_table), first,
+                            std::min<uint64_t>(lease.piece, t->n_points - first), radius, d_radii, max_count, shortcut,
+                            d_counts, lease.stack, t->slots, s);
+  return rc;
+}
+
+int ptk_search64_count_within_self_device(const ptk_tree64* t, double radius, const double* d_radii, uint64_t max_count,
+                                          uint64_t* d_counts, void* stream) {
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_counts, "count_within_self",
+                             "kd_tree::search_radius_self, one point at a time");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = count_table64_of(t, s);
+  if (rc != PTK_OK) return rc;
+  Stack64Lease lease(t, s);
+  rc = lease.acquire(t->n_points);
+  if (rc != PTK_OK) return rc;
+  return count64_self_pieces(t, radius, d_radii, max_count, d_counts, s, lease);
+}
+
+int ptk_search64_count_within_self(const ptk_tree64* t, double radius, const double* radii, uint64_t max_count,
+                                   uint64_t* counts) {
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, counts, "count_within_self",
+                             "kd_tree::search_radius_self, one point at a time");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bin, bout;
+  const uint64_t np = t->n_points;
+  hipError_t he = bout.get(t, 1, np * 8);
+  const double* d_radii = nullptr;
+  if (he == hipSuccess && radii != nullptr) {
+    he = bin.get(t, 0, np * sizeof(double));
+    if (he == hipSuccess) he = hipMemcpy(bin.p, radii, np * sizeof(double), hipMemcpyHostToDevice);
+    d_radii = reinterpret_cast<const double*>(bin.p);
+  }
+  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (the buffers of count_within_self): %s", hipGetErrorString(he));
+  rc = ptk_search64_count_within_self_device(t, radius, d_radii, max_count, reinterpret_cast<uint64_t*>(bout.p), nullptr);
+  if (rc != PTK_OK) return rc;
+  he = hipMemcpy(counts, bout.p, np * 8, hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  return PTK_OK;
+}
+
+// ptk_search_radius_self in double: the count (max_count = 0), the scan and the fill on the device.
+int ptk_search64_radius_self(const ptk_tree64* t, double radius, const double* radii, int sort, uint64_t* offsets,
+                             ptk_neighbor64** out) {
+  if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
+  *out = nullptr;
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, offsets, "search_radius_self",
+                             "kd_tree::search_radius_self, one point at a time");
+  if (rc != PTK_OK) return rc;
+  offsets[0] = 0;
+  const uint64_t np = t->n_points;
+  if (np == 0) return PTK_OK;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bin, bout;
+  const size_t c_room = ((np + 1) * 8 + 255) & ~size_t(255);
+  hipError_t he = bin.get(t, 0, 3 * c_room);
+  double* d_r = reinterpret_cast<double*>(bin.p);
+  uint64_t* d_c = reinterpret_cast<uint64_t*>(bin.p + c_room);
+  uint64_t* d_o = reinterpret_cast<uint64_t*>(bin.p + 2 * c_room);
+  if (he == hipSuccess) he = hipMemset(d_c, 0, (np + 1) * 8);
+  if (he == hipSuccess && radii != nullptr) he = hipMemcpy(d_r, radii, np * sizeof(double), hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    const double* d_radii = radii != nullptr ? d_r : nullptr;
+    rc = ptk_search64_count_within_self_device(t, radius, d_radii, 0, d_c, nullptr);
+    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, np, offsets);
+    if (rc == PTK_OK) {
+      const size_t obytes = std::max<uint64_t>(offsets[np], 1) * sizeof(ptk_neighbor64);
+      he = bout.get(t, 1, obytes);
+      ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(bout.p);
+      if (he == hipSuccess) {
+        Stack64Lease lease(t, nullptr);
+        rc = lease.acquire(np);
+        for (uint64_t first = 0; first < np && rc == PTK_OK; first += lease.piece)
+          rc = ptkf::radius64_self_fill(t->dev, t->metric.load(), first, std::min<uint64_t>(lease.piece, np - first), radius,
+                                        d_radii, d_o, d_out, lease.stack, t->slots, nullptr);
+        if (rc == PTK_OK && sort) {
+          hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((np + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock),
+                             0, nullptr, d_o, np, d_out);
+          he = hipGetLastError();
+        }
+      }
+      if (he == hipSuccess && rc == PTK_OK) {
+        *out = static_cast<ptk_neighbor64*>(std::malloc(obytes));
+        if (*out == nullptr) {
+          rc = fail(PTK_ERR_NOMEM, "out of memory");
+        } else {
+          he = hipMemcpy(*out, bout.p, obytes, hipMemcpyDeviceToHost);
+        }
+      }
+    }
+  }
+  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  if (rc != PTK_OK && *out) {
+    std::free(*out);
+    *out = nullptr;
+  }
+  return rc;
+}
+
 int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs, uint64_t nb, uint64_t* offsets,
                      int32_t** out) {
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");

@@ -138,6 +138,18 @@ int self_queries64(const double* pts, uint32_t stride, uint32_t dim, uint64_t fi
 int drop_self(const ptk::Neighbor* rows, const float4* recs, const int32_t* index, uint64_t first, uint64_t n, uint32_t k,
               ptk::Neighbor* d_out, hipStream_t s);
 int drop_self64(const void* rows, const int32_t* index, uint64_t first, uint64_t n, uint32_t k, void* d_out, hipStream_t s);
+// search_radius_self / count_within_self (ptk_kernels_selfr.hpp): leaf positions [first, first + n) of a handle
+// ptk_search_count_within_radii serves (check_radius_self); d_radii null: every point gets `radius`, else radii by original
+// point index.  The float32 forms read the handle's count side table (built before: count_table_of).
+int count_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t max_count,
+               bool shortcut, uint64_t* d_counts, hipStream_t s);
+int radius_self_fill(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                     const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s);
+int count64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, uint64_t first, uint64_t n,
+                 double radius, const double* d_radii, uint64_t max_count, bool shortcut, uint64_t* d_counts,
+                 ptk::Rec64* stack, uint32_t slots, hipStream_t s);
+int radius64_self_fill(const ptk::DevTree64& dev, int metric, uint64_t first, uint64_t n, double radius, const double* d_radii,
+                       const uint64_t* d_offsets, void* d_out, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
 void warm_self();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.

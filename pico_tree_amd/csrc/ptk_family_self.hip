@@ -1,11 +1,13 @@
 // ptk_family_self.hip -- search_knn_self: the direct kernel over the tree's own leaf-order
 // records (3-D float32 trees, the four non-topological metrics, k + 1 <= 64) and the two small kernels of the staged route
 // (the piece's points as query rows; the rule of the contract on the rows the handle's own search returned), float32 and
-// float64.
+// float64; search_radius_self / count_within_self (ptk_kernels_selfr.hpp, K18): the count and fill kernels over the tree's
+// own records, float32 and float64, each written once over its radius source.
 // One of the translation units of libptk.so (ptk_backend_core.hpp).
 
 #include "ptk_families.hpp"
 #include "ptk_kernels_f64.hpp"
+#include "ptk_kernels_selfr.hpp"
 
 namespace {
 
@@ -26,6 +28,72 @@ int launch_knn_self(const ptk_tree* t, uint64_t first, uint64_t n, uint32_t k, p
 #undef PTK_LAUNCH_SELF
   PTK_HIP(hipGetLastError());
   timer.stop(0, n);
+  return PTK_OK;
+}
+
+// count_within_self / search_radius_self: leaf positions [first, first + n); d_radii null: every point gets `radius`.
+template <int S, int OVF, class M>
+int launch_count_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t max_count,
+                      bool shortcut, uint64_t* d_counts, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  const auto* table = static_cast<const ptk::CountBox*>(t->d_count_table);
+  Timer timer(t, s);
+  if (d_radii != nullptr)
+    hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                       t->dev, table, t->dim, first, n, radius, d_radii, max_count, shortcut ? 1u : 0u, d_counts, nullptr);
+  else
+    hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                       t->dev, table, t->dim, first, n, radius, d_radii, max_count, shortcut ? 1u : 0u, d_counts, nullptr);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, n);
+  return PTK_OK;
+}
+
+template <int S, int OVF, class M>
+int launch_radius_self_fill(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                            const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  Timer timer(t, s);
+  if (d_radii != nullptr)
+    hipLaunchKernelGGL((ptk::radius_self_fill_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64),
+                       (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, d_offsets, d_out);
+  else
+    hipLaunchKernelGGL((ptk::radius_self_fill_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64),
+                       (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, d_offsets, d_out);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, n);
+  return PTK_OK;
+}
+
+template <class M>
+int launch_count64_self(const ptk::DevTree64& dev, const ptk::CountBox64* table, uint64_t first, uint64_t n, double radius,
+                        const double* d_radii, uint64_t max_count, bool shortcut, uint64_t* d_counts, ptk::Rec64* stack,
+                        uint32_t slots, hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+  const size_t smem = ptk::lds64_bytes(0, dev.dim);
+  if (d_radii != nullptr)
+    hipLaunchKernelGGL((ptk::count64_self_kernel<M, true>), grid, block, smem, s, dev, table, first, n, radius, d_radii,
+                       max_count, shortcut ? 1u : 0u, d_counts, stack, slots, nullptr);
+  else
+    hipLaunchKernelGGL((ptk::count64_self_kernel<M, false>), grid, block, smem, s, dev, table, first, n, radius, d_radii,
+                       max_count, shortcut ? 1u : 0u, d_counts, stack, slots, nullptr);
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+template <class M>
+int launch_radius64_self_fill(const ptk::DevTree64& dev, uint64_t first, uint64_t n, double radius, const double* d_radii,
+                              const uint64_t* d_offsets, ptk::Neighbor64* d_out, ptk::Rec64* stack, uint32_t slots,
+                              hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+  const size_t smem = ptk::lds64_bytes(0, dev.dim);
+  if (d_radii != nullptr)
+    hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, true>), grid, block, smem, s, dev, first, n, radius, d_radii,
+                       d_offsets, d_out, stack, slots);
+  else
+    hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, false>), grid, block, smem, s, dev, first, n, radius, d_radii,
+                       d_offsets, d_out, stack, slots);
+  PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
 
@@ -71,6 +139,52 @@ int drop_self64(const void* rows, const int32_t* index, uint64_t first, uint64_t
                      ptk::kDblMax, static_cast<ptk::Neighbor64*>(d_out));
   PTK_HIP(hipGetLastError());
   return PTK_OK;
+}
+
+int count_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t max_count,
+               bool shortcut, uint64_t* d_counts, hipStream_t s) {
+  if (t->dim > 3) return fail(PTK_ERR_INVALID, "count_self: not a call of the self kernels");
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_self<16, OVF, M>(t, first, n, radius, d_radii, max_count, shortcut, d_counts, s))));
+  return rc;
+}
+
+int radius_self_fill(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                     const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
+  if (t->dim > 3) return fail(PTK_ERR_INVALID, "radius_self_fill: not a call of the self kernels");
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_radius_self_fill<16, OVF, M>(t, first, n, radius, d_radii, d_offsets, d_out, s))));
+  return rc;
+}
+
+int count64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, uint64_t first, uint64_t n,
+                 double radius, const double* d_radii, uint64_t max_count, bool shortcut, uint64_t* d_counts,
+                 ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
+  switch (metric) {
+    case PTK_METRIC_L1:
+      return launch_count64_self<ptk::Metric64L1>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
+    case PTK_METRIC_LPINF:
+      return launch_count64_self<ptk::Metric64LInf>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
+    case PTK_METRIC_LNINF:
+      return launch_count64_self<ptk::Metric64LNInf>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
+    default:
+      return launch_count64_self<ptk::Metric64L2>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
+  }
+}
+
+int radius64_self_fill(const ptk::DevTree64& dev, int metric, uint64_t first, uint64_t n, double radius, const double* d_radii,
+                       const uint64_t* d_offsets, void* d_out, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
+  auto* o = static_cast<ptk::Neighbor64*>(d_out);
+  switch (metric) {
+    case PTK_METRIC_L1:
+      return launch_radius64_self_fill<ptk::Metric64L1>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
+    case PTK_METRIC_LPINF:
+      return launch_radius64_self_fill<ptk::Metric64LInf>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
+    case PTK_METRIC_LNINF:
+      return launch_radius64_self_fill<ptk::Metric64LNInf>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
+    default:
+      return launch_radius64_self_fill<ptk::Metric64L2>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
+  }
 }
 
 // (loads this unit's code object on the calling thread's device: ProcessWarmup of ptk_backend.hip)

@@ -225,6 +225,32 @@ int radius_rows(const ptk_tree* t, const float* points, const float* q, uint64_t
   return PTK_OK;
 }
 
+// search_radius_self (ptk.h) as the contract reads: the reference's radius search of each of the tree's own points, then
+// the removal of the entry whose index is the row's (an index occurs at most once in a row).  per_row[i]: row i.
+template <class RadiusOf>
+void radius_self_rows(const ptk_tree* t, const flat_t& flat, const view_t& view, const float* points, int sort,
+                      std::vector<std::vector<neighbor_t>>& per_row, RadiusOf&& radius_of) {
+  rows_loop(t->n_points, [&](uint64_t i) {
+    std::vector<neighbor_t>& row = per_row[i];
+    internal::radius_visitor<neighbor_t> v(radius_of(i), row);
+    search_one(t, flat, view, points + i * t->dim, v);
+    if (sort) v.sort();
+    for (size_t j = 0; j < row.size(); ++j) {
+      if (row[j].index == (int)i) {
+        row.erase(row.begin() + (std::ptrdiff_t)j);
+        break;
+      }
+    }
+  });
+}
+
+// The argument checks of the two self loops: `radii` null -> the scalar radius; else n_points entries, scanned by row.
+inline int check_host_self(const ptk_tree* t, const float* points, float radius, const float* radii) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  if (radii == nullptr) return radius >= 0.0f ? PTK_OK : fail(PTK_ERR_INVALID, "radius must be >= 0 (and not NaN)");
+  return check_radii(radii, t->n_points, /*host_values=*/true);
+}
+
 }  // namespace ptk_host
 
 extern "C" {
@@ -367,6 +393,61 @@ int ptk_host_search_radius_radii(const ptk_tree* t, const float* points, const f
     if (rc != PTK_OK) return rc;
   }
   return ptk_host::radius_rows(t, points, q, nq, 1.0f, sort, offsets, out, [radii](uint64_t i) { return radii[i]; });
+}
+
+int ptk_host_search_count_within_self(const ptk_tree* t, const float* points, float radius, const float* radii,
+                                      uint64_t max_count, uint64_t* counts) {
+  const int rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc != PTK_OK) return rc;
+  if (counts == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null counts buffer");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    std::vector<std::vector<neighbor_t>> per_row(t->n_points);
+    radius_self_rows(t, flat, view, points, 0, per_row, [&](uint64_t i) { return radii != nullptr ? radii[i] : radius; });
+    // (the clamp after the own entry has left)
+    for (uint64_t i = 0; i < t->n_points; ++i)
+      counts[i] = max_count != 0 ? std::min<uint64_t>(per_row[i].size(), max_count) : per_row[i].size();
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+int ptk_host_search_radius_self(const ptk_tree* t, const float* points, float radius, const float* radii, int sort,
+                                uint64_t* offsets, ptk_neighbor** out) {
+  if (offsets == nullptr || out == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  *out = nullptr;
+  const int rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc != PTK_OK) return rc;
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    const uint64_t np = t->n_points;
+    std::vector<std::vector<neighbor_t>> per_row(np);
+    radius_self_rows(t, flat, view, points, sort, per_row, [&](uint64_t i) { return radii != nullptr ? radii[i] : radius; });
+    offsets[0] = 0;
+    for (uint64_t i = 0; i < np; ++i) offsets[i + 1] = offsets[i] + per_row[i].size();
+    auto* rows = static_cast<neighbor_t*>(std::malloc(std::max<size_t>(offsets[np], 1) * sizeof(neighbor_t)));
+    if (rows == nullptr) return fail(PTK_ERR_NOMEM, "out of host memory");
+    for (uint64_t i = 0; i < np; ++i) std::copy(per_row[i].begin(), per_row[i].end(), rows + offsets[i]);
+    *out = reinterpret_cast<ptk_neighbor*>(rows);
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
 }
 
 int ptk_host_search_box(const ptk_tree* t, const float* points, const float* mins, const float* maxs, uint64_t nb,
