@@ -12,6 +12,7 @@
 #include "ptk_build.hpp"
 #include "ptk_sort.hpp"
 #include "ptk_forest.hpp"
+#include "ptk_rows_out.hpp"
 
 namespace {
 
@@ -2087,6 +2088,16 @@ int ptk_search_count_within_radii(const ptk_tree* t, const float* q, uint64_t nq
 
 // ---- radius -------------------------------------------------------------------------------
 
+// Rows ascending by distance, in place: one lane per row.
+static int sort_rows(const ptk_tree* t, uint64_t n, const uint64_t* d_offsets, ptk::Neighbor* o, hipStream_t s) {
+  Timer timer(t, s);
+  const uint32_t blocks = (uint32_t)((n + ptk::kBlock - 1) / ptk::kBlock);
+  hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, n, d_offsets, o);
+  PTK_HIP(hipGetLastError());
+  timer.stop(2, 0);
+  return PTK_OK;
+}
+
 static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, float e, bool fill,
                               uint64_t* d_counts, const uint64_t* d_offsets, ptk_neighbor* d_out, int sort,
                               hipStream_t s) {
@@ -2172,13 +2183,7 @@ static int radius_pass_device(const ptk_tree* t, const float* d_q, uint64_t nq, 
       rc = ptkf::radius_traverse(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets, o, s);
     }
   }
-  if (rc == PTK_OK && fill && sort) {
-    Timer timer(t, s);
-    const uint32_t blocks = (uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock);
-    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, nq, d_offsets, o);
-    PTK_HIP(hipGetLastError());
-    timer.stop(2, 0);
-  }
+  if (rc == PTK_OK && fill && sort) rc = sort_rows(t, nq, d_offsets, o, s);
   return rc;
 }
 
@@ -2255,24 +2260,10 @@ int ptk_search_radius_fill(const ptk_tree* t, const float* q, uint64_t nq, float
   return PTK_OK;
 }
 
-// counts (n + 1, the last one 0) -> offsets (n + 1) on the device, the offsets copied to the host.
-static hipError_t scan_counts(uint64_t* d_c, uint64_t* d_o, uint64_t n, uint64_t* offsets) {
-  size_t tmp_bytes = 0;
-  DeviceBlock tmp;
-  hipError_t he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(),
-                                          (hipStream_t) nullptr);
-  if (he == hipSuccess) he = tmp.alloc(tmp_bytes ? tmp_bytes : 16);
-  if (he == hipSuccess)
-    he = rocprim::exclusive_scan(tmp.p, tmp_bytes, d_c, d_o, (uint64_t)0, n + 1, rocprim::plus<uint64_t>(),
-                                 (hipStream_t) nullptr);
-  if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (n + 1) * 8, hipMemcpyDeviceToHost);
-  return he;
-}
-
 int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radius, float e, int sort,
                       uint64_t* offsets, ptk_neighbor** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_search(t, q, nq);
   if (rc != PTK_OK) return rc;
   offsets[0] = 0;
@@ -2284,36 +2275,14 @@ int ptk_search_radius(const ptk_tree* t, const float* q, uint64_t nq, float radi
   hipError_t he = d_q.alloc(qbytes);
   if (he == hipSuccess) he = d_c.alloc((nq + 1) * 8);
   if (he == hipSuccess) he = d_o.alloc((nq + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nq + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(d_q.p, q, qbytes, hipMemcpyHostToDevice);
-  uint64_t total = 0;
-  if (he == hipSuccess) {
-    rc = ptk_search_radius_count_device(t, d_q.as<float>(), nq, radius, e, d_c.as<uint64_t>(), nullptr);
-    if (rc == PTK_OK) {
-      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nq, offsets);
-      if (he == hipSuccess) {
-        total = offsets[nq];
-        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
-      }
-      if (he == hipSuccess)
-        rc = ptk_search_radius_fill_device(t, d_q.as<float>(), nq, radius, e, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort,
-                                           nullptr);
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else if (total > 0) {
-          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
+  rc = rows_to_host(
+      he, nq, d_c.as<uint64_t>(), d_o.as<uint64_t>(), offsets, out, rows_in<ptk_neighbor>(d_out),
+      [&](uint64_t* d_counts) { return ptk_search_radius_count_device(t, d_q.as<float>(), nq, radius, e, d_counts, nullptr); },
+      [&](const uint64_t* d_offsets, ptk_neighbor* d_rows, uint64_t) {
+        return ptk_search_radius_fill_device(t, d_q.as<float>(), nq, radius, e, d_offsets, d_rows, sort, nullptr);
+      });
   drop_radius_capture(t);
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
   return rc;
 }
 
@@ -2335,21 +2304,15 @@ int ptk_search_radius_radii_fill_device(const ptk_tree* t, const float* d_q, uin
   rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, ptk::kCellsDenseFirst);
   if (rc != PTK_OK) return rc;
   rc = ptkf::radius_radii_fill(t, d_q, perm, nq, d_radii, d_offsets, o, s);
-  if (rc == PTK_OK && sort) {
-    Timer timer(t, s);
-    const uint32_t blocks = (uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock);
-    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, nq, d_offsets, o);
-    PTK_HIP(hipGetLastError());
-    timer.stop(2, 0);
-  }
+  if (rc == PTK_OK && sort) rc = sort_rows(t, nq, d_offsets, o, s);
   return rc;
 }
 
 // Convenience, as ptk_search_radius: the count, the scan and the fill on the device; the radii go up beside the queries.
 int ptk_search_radius_radii(const ptk_tree* t, const float* q, uint64_t nq, const float* radii, int sort, uint64_t* offsets,
                             ptk_neighbor** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_radius_radii(t, q, nq, radii, offsets, /*host_values=*/true);
   if (rc != PTK_OK) return rc;
   offsets[0] = 0;
@@ -2361,38 +2324,16 @@ int ptk_search_radius_radii(const ptk_tree* t, const float* q, uint64_t nq, cons
   hipError_t he = d_in.alloc(qbytes + nq * sizeof(float));
   if (he == hipSuccess) he = d_c.alloc((nq + 1) * 8);
   if (he == hipSuccess) he = d_o.alloc((nq + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nq + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(d_in.p, q, qbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(static_cast<char*>(d_in.p) + qbytes, radii, nq * sizeof(float), hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    const float* d_q = d_in.as<float>();
-    const float* d_radii = d_q + nq * t->dim;
-    uint64_t total = 0;
-    rc = ptk_search_count_within_radii_device(t, d_q, nq, d_radii, 0, d_c.as<uint64_t>(), nullptr);
-    if (rc == PTK_OK) {
-      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nq, offsets);
-      if (he == hipSuccess) {
-        total = offsets[nq];
-        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
-      }
-      if (he == hipSuccess)
-        rc = ptk_search_radius_radii_fill_device(t, d_q, nq, d_radii, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort, nullptr);
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else if (total > 0) {
-          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  const float* d_q = d_in.as<float>();
+  const float* d_radii = d_q + nq * t->dim;
+  return rows_to_host(
+      he, nq, d_c.as<uint64_t>(), d_o.as<uint64_t>(), offsets, out, rows_in<ptk_neighbor>(d_out),
+      [&](uint64_t* d_counts) { return ptk_search_count_within_radii_device(t, d_q, nq, d_radii, 0, d_counts, nullptr); },
+      [&](const uint64_t* d_offsets, ptk_neighbor* d_rows, uint64_t) {
+        return ptk_search_radius_radii_fill_device(t, d_q, nq, d_radii, d_offsets, d_rows, sort, nullptr);
+      });
 }
 
 // ---- the radius searches of the tree's own points (ptk.h) -----------------------
@@ -2429,13 +2370,7 @@ int ptk_search_radius_self_fill_device(const ptk_tree* t, float radius, const fl
   rc = in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
     return ptkf::radius_self_fill(t, first, n, radius, d_radii, d_offsets, o, s);
   });
-  if (rc == PTK_OK && sort) {
-    Timer timer(t, s);
-    const uint32_t blocks = (uint32_t)((t->n_points + ptk::kBlock - 1) / ptk::kBlock);
-    hipLaunchKernelGGL(ptk::sort_rows_kernel, dim3(blocks), dim3(ptk::kBlock), 0, s, t->n_points, d_offsets, o);
-    PTK_HIP(hipGetLastError());
-    timer.stop(2, 0);
-  }
+  if (rc == PTK_OK && sort) rc = sort_rows(t, t->n_points, d_offsets, o, s);
   return rc;
 }
 
@@ -2472,8 +2407,8 @@ int ptk_search_count_within_self(const ptk_tree* t, float radius, const float* r
 // Convenience, as ptk_search_radius_radii: the count, the scan and the fill on the device.
 int ptk_search_radius_self(const ptk_tree* t, float radius, const float* radii, int sort, uint64_t* offsets,
                            ptk_neighbor** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_radius_self(t, radius, radii, /*host_values=*/true, offsets, "search_radius_self",
                              "ptk_host_search_radius_self");
   if (rc != PTK_OK) return rc;
@@ -2485,37 +2420,15 @@ int ptk_search_radius_self(const ptk_tree* t, float radius, const float* radii, 
   DeviceBlock d_r, d_c, d_o, d_out;
   hipError_t he = d_c.alloc((np + 1) * 8);
   if (he == hipSuccess) he = d_o.alloc((np + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (np + 1) * 8);
   if (he == hipSuccess && radii != nullptr) he = d_r.alloc(np * sizeof(float));
   if (he == hipSuccess && radii != nullptr) he = hipMemcpy(d_r.p, radii, np * sizeof(float), hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    const float* d_radii = radii != nullptr ? d_r.as<float>() : nullptr;
-    uint64_t total = 0;
-    rc = ptk_search_count_within_self_device(t, radius, d_radii, 0, d_c.as<uint64_t>(), nullptr);
-    if (rc == PTK_OK) {
-      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), np, offsets);
-      if (he == hipSuccess) {
-        total = offsets[np];
-        he = d_out.alloc(std::max<uint64_t>(total, 1) * 8);
-      }
-      if (he == hipSuccess)
-        rc = ptk_search_radius_self_fill_device(t, radius, d_radii, d_o.as<uint64_t>(), d_out.as<ptk_neighbor>(), sort, nullptr);
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor*>(std::malloc(std::max<uint64_t>(total, 1) * 8));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else if (total > 0) {
-          he = hipMemcpy(*out, d_out.p, total * 8, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  const float* d_radii = d_r.as<float>();  // (null without per-row radii)
+  return rows_to_host(
+      he, np, d_c.as<uint64_t>(), d_o.as<uint64_t>(), offsets, out, rows_in<ptk_neighbor>(d_out),
+      [&](uint64_t* d_counts) { return ptk_search_count_within_self_device(t, radius, d_radii, 0, d_counts, nullptr); },
+      [&](const uint64_t* d_offsets, ptk_neighbor* d_rows, uint64_t) {
+        return ptk_search_radius_self_fill_device(t, radius, d_radii, d_offsets, d_rows, sort, nullptr);
+      });
 }
 
 }  // extern "C"
@@ -2628,8 +2541,8 @@ int ptk_search_box_fill_device(const ptk_tree* t, const float* d_mins, const flo
 
 int ptk_search_box(const ptk_tree* t, const float* mins, const float* maxs, uint64_t nb, uint64_t* offsets,
                    int32_t** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_search(t, mins, nb);
   if (rc != PTK_OK) return rc;
   if (nb > 0 && maxs == nullptr) return fail(PTK_ERR_INVALID, "null box buffer");
@@ -2643,37 +2556,16 @@ int ptk_search_box(const ptk_tree* t, const float* mins, const float* maxs, uint
   if (he == hipSuccess) he = d_mx.alloc(bbytes);
   if (he == hipSuccess) he = d_c.alloc((nb + 1) * 8);
   if (he == hipSuccess) he = d_o.alloc((nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(d_c.p, 0, (nb + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(d_mn.p, mins, bbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(d_mx.p, maxs, bbytes, hipMemcpyHostToDevice);
-  uint64_t total = 0;
-  if (he == hipSuccess) {
-    rc = ptk_search_box_count_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_c.as<uint64_t>(), nullptr);
-    if (rc == PTK_OK) {
-      he = scan_counts(d_c.as<uint64_t>(), d_o.as<uint64_t>(), nb, offsets);
-      if (he == hipSuccess) {
-        total = offsets[nb];
-        he = d_out.alloc(std::max<uint64_t>(total, 1) * 4);
-      }
-      if (he == hipSuccess)
-        rc = ptk_search_box_fill_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_o.as<uint64_t>(), d_out.as<int32_t>(),
-                                        nullptr);
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<int32_t*>(std::malloc(std::max<uint64_t>(total, 1) * 4));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else if (total > 0) {
-          he = hipMemcpy(*out, d_out.p, total * 4, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  return rows_to_host(
+      he, nb, d_c.as<uint64_t>(), d_o.as<uint64_t>(), offsets, out, rows_in<int32_t>(d_out),
+      [&](uint64_t* d_counts) {
+        return ptk_search_box_count_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_counts, nullptr);
+      },
+      [&](const uint64_t* d_offsets, int32_t* d_rows, uint64_t) {
+        return ptk_search_box_fill_device(t, d_mn.as<float>(), d_mx.as<float>(), nb, d_offsets, d_rows, nullptr);
+      });
 }
 
 void ptk_free(void* p) { std::free(p); }

@@ -10,6 +10,7 @@
 
 #include "ptk_kernels_f64.hpp"
 #include "ptk_kernels_coop64.hpp"
+#include "ptk_rows_out.hpp"
 
 static_assert(sizeof(ptk_neighbor64) == 16 && offsetof(ptk_neighbor64, distance) == 8, "neighbor<int, double> layout");
 
@@ -217,6 +218,16 @@ struct IoBuffer {
     return hipMalloc((void**)&p, bytes);
   }
 };
+
+// The rows of a ragged host form (rows_to_host) in block 1 of the handle.
+template <class Row>
+auto rows_in(const ptk_tree64* t, IoBuffer& block) {
+  return [t, &block](size_t bytes, Row** d_rows) {
+    const hipError_t he = block.get(t, 1, bytes);
+    *d_rows = reinterpret_cast<Row*>(block.p);
+    return he;
+  };
+}
 
 // The host-buffer form of a search whose rows have one size: under the handle's I/O lock the batch goes up into block 0,
 // `search(d_q, d_out)` -- the _device form, on the null stream -- fills block 1, and that comes down.  `records`: the rows
@@ -776,18 +787,11 @@ int launch_box64(const ptk_tree64* t, const double* d_mins, const double* d_maxs
   return PTK_OK;
 }
 
-// counts (nq + 1, last = 0) -> offsets (nq + 1) on the device, offsets copied to the host.
-int scan_counts64(uint64_t* d_c, uint64_t* d_o, uint64_t nq, uint64_t* offsets) {
-  size_t tmp_bytes = 0;
-  DeviceBlock tmp;
-  hipError_t he = rocprim::exclusive_scan(nullptr, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
-                                          (hipStream_t) nullptr);
-  if (he == hipSuccess) he = tmp.alloc(tmp_bytes ? tmp_bytes : 16);
-  if (he == hipSuccess)
-    he = rocprim::exclusive_scan(tmp.p, tmp_bytes, d_c, d_o, (uint64_t)0, nq + 1, rocprim::plus<uint64_t>(),
-                                 (hipStream_t) nullptr);
-  if (he == hipSuccess) he = hipMemcpy(offsets, d_o, (nq + 1) * 8, hipMemcpyDeviceToHost);
-  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error in the offsets scan: %s", hipGetErrorString(he));
+// Rows ascending by distance, in place, on the null stream: one lane per row.
+int sort_rows64(uint64_t n, const uint64_t* d_offsets, ptk::Neighbor64* d_out) {
+  hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((n + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock), 0,
+                     nullptr, d_offsets, n, d_out);
+  PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
 
@@ -1239,8 +1243,8 @@ int ptk_search64_knn(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t
 
 int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, double radius, double e, int sort,
                         uint64_t* offsets, ptk_neighbor64** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_search(t, q, nq);
   if (rc == PTK_OK) rc = check_ratio(e);
   if (rc != PTK_OK) return rc;
@@ -1256,71 +1260,51 @@ int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, doubl
   double* d_q = reinterpret_cast<double*>(bin.p);
   uint64_t* d_c = reinterpret_cast<uint64_t*>(bin.p + q_room);
   uint64_t* d_o = reinterpret_cast<uint64_t*>(bin.p + q_room + c_room);
-  ptk_neighbor64* d_out = nullptr;
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (nq + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
-  uint64_t total = 0;
-  if (he == hipSuccess) {
-    Stack64Lease lease(t, nullptr);
-    uint32_t cap = radius64_cap(t, nq);
-    const uint32_t* perm = nullptr;
-    rc = order_batch64(t, d_q, nq, nullptr, lease, cap != 0u ? radius64_coop_scratch_bytes(t, nq) : 0, &perm);
-    if (rc == PTK_ERR_NOMEM && cap != 0u) {  // (no room for the hand-over list: the uncapped search needs none)
-      cap = 0u;
-      rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
-    }
-    Radius64Scratch rs;
-    if (rc == PTK_OK && cap != 0u) {
-      rs = radius64_carve(t, nq, lease.own);
-      t->last_meta = rs.meta;
-      PTK_WITH_EUCLID64(rc = (launch_radius64_capped<M, false>(t, d_q, perm, nq, radius, e, cap, d_c, nullptr, nullptr, nullptr,
-                                                              lease, rs)));
-    } else if (rc == PTK_OK) {
-      PTK_WITH_METRIC64(rc = (launch_radius64<M, false>(t, d_q, perm, nq, radius, e, d_c, nullptr, nullptr, nullptr, lease)));
-    }
-    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, nq, offsets);
-    if (rc == PTK_OK) {
-      total = offsets[nq];
-      const size_t obytes = std::max<uint64_t>(total, 1) * sizeof(ptk_neighbor64);
-      he = bout.get(t, 1, obytes);
-      d_out = reinterpret_cast<ptk_neighbor64*>(bout.p);
-      if (he == hipSuccess) he = hipMemset(d_out, 0, obytes);
-      if (he == hipSuccess && cap != 0u) {
-        PTK_WITH_EUCLID64(rc = (launch_radius64_capped<M, true>(t, d_q, perm, nq, radius, e, cap, nullptr, d_o,
-                                                               reinterpret_cast<ptk::Neighbor64*>(d_out), nullptr, lease, rs)));
-      } else if (he == hipSuccess) {
-        PTK_WITH_METRIC64(rc = (launch_radius64<M, true>(t, d_q, perm, nq, radius, e, nullptr, d_o,
-                                                         reinterpret_cast<ptk::Neighbor64*>(d_out), nullptr, lease)));
-      }
-      if (he == hipSuccess && rc == PTK_OK && sort) {
-        hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock),
-                           0, nullptr, d_o, nq, reinterpret_cast<ptk::Neighbor64*>(d_out));
-        he = hipGetLastError();
-      }
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor64*>(std::malloc(obytes));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else {
-          he = hipMemcpy(*out, d_out, obytes, hipMemcpyDeviceToHost);
+  // The lease, the batch order and the capped call's scratch are the count pass's and stay for the fill pass.
+  Stack64Lease lease(t, nullptr);
+  uint32_t cap = radius64_cap(t, nq);
+  const uint32_t* perm = nullptr;
+  Radius64Scratch rs;
+  return rows_to_host(
+      he, nq, d_c, d_o, offsets, out, rows_in<ptk_neighbor64>(t, bout),
+      [&](uint64_t* d_counts) {
+        int rc = order_batch64(t, d_q, nq, nullptr, lease, cap != 0u ? radius64_coop_scratch_bytes(t, nq) : 0, &perm);
+        if (rc == PTK_ERR_NOMEM && cap != 0u) {  // (no room for the hand-over list: the uncapped search needs none)
+          cap = 0u;
+          rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
         }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+        if (rc == PTK_OK && cap != 0u) {
+          rs = radius64_carve(t, nq, lease.own);
+          t->last_meta = rs.meta;
+          PTK_WITH_EUCLID64(rc = (launch_radius64_capped<M, false>(t, d_q, perm, nq, radius, e, cap, d_counts, nullptr, nullptr,
+                                                                  nullptr, lease, rs)));
+        } else if (rc == PTK_OK) {
+          PTK_WITH_METRIC64(
+              rc = (launch_radius64<M, false>(t, d_q, perm, nq, radius, e, d_counts, nullptr, nullptr, nullptr, lease)));
+        }
+        return rc;
+      },
+      [&](const uint64_t* d_offsets, ptk_neighbor64* d_rows, uint64_t) {
+        ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(d_rows);
+        int rc = PTK_OK;
+        if (cap != 0u) {
+          PTK_WITH_EUCLID64(
+              rc = (launch_radius64_capped<M, true>(t, d_q, perm, nq, radius, e, cap, nullptr, d_offsets, d_out, nullptr, lease, rs)));
+        } else {
+          PTK_WITH_METRIC64(rc = (launch_radius64<M, true>(t, d_q, perm, nq, radius, e, nullptr, d_offsets, d_out, nullptr, lease)));
+        }
+        if (rc == PTK_OK && sort) rc = sort_rows64(nq, d_offsets, d_out);
+        return rc;
+      });
 }
 
 // ptk_search_radius_radii in double: the per-row count (max_count = 0), the scan and the fill on the device, the radii
 // beside the queries.  The handles ptk_search64_count_within_radii serves; the rest is refused by the same check.
 int ptk_search64_radius_radii(const ptk_tree64* t, const double* q, uint64_t nq, const double* radii, int sort,
                               uint64_t* offsets, ptk_neighbor64** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_radius_radii(t, q, nq, radii, offsets, /*host_values=*/true);
   if (rc != PTK_OK) return rc;
   offsets[0] = 0;
@@ -1336,45 +1320,21 @@ int ptk_search64_radius_radii(const ptk_tree64* t, const double* q, uint64_t nq,
   double* d_r = reinterpret_cast<double*>(bin.p + q_room);
   uint64_t* d_c = reinterpret_cast<uint64_t*>(bin.p + q_room + c_room);
   uint64_t* d_o = reinterpret_cast<uint64_t*>(bin.p + q_room + 2 * c_room);
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (nq + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(d_q, q, qbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(d_r, radii, nq * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    rc = ptk_search64_count_within_radii_device(t, d_q, nq, d_r, 0, d_c, nullptr);
-    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, nq, offsets);
-    if (rc == PTK_OK) {
-      const size_t obytes = std::max<uint64_t>(offsets[nq], 1) * sizeof(ptk_neighbor64);
-      he = bout.get(t, 1, obytes);
-      ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(bout.p);
-      if (he == hipSuccess) he = hipMemset(d_out, 0, obytes);  // (the padding bytes of the records: no kernel writes them)
-      if (he == hipSuccess) {
+  return rows_to_host(
+      he, nq, d_c, d_o, offsets, out, rows_in<ptk_neighbor64>(t, bout),
+      [&](uint64_t* d_counts) { return ptk_search64_count_within_radii_device(t, d_q, nq, d_r, 0, d_counts, nullptr); },
+      [&](const uint64_t* d_offsets, ptk_neighbor64* d_rows, uint64_t) {
+        ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(d_rows);
         Stack64Lease lease(t, nullptr);
         const uint32_t* perm = nullptr;
-        rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
+        int rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
         if (rc == PTK_OK)
-          PTK_WITH_EUCLID64(rc = (launch_radius64_radii_fill<M>(t, d_q, perm, nq, d_r, d_o, d_out, nullptr, lease)));
-        if (rc == PTK_OK && sort) {
-          hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((nq + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock),
-                             0, nullptr, d_o, nq, d_out);
-          he = hipGetLastError();
-        }
-      }
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor64*>(std::malloc(obytes));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else {
-          he = hipMemcpy(*out, bout.p, obytes, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+          PTK_WITH_EUCLID64(rc = (launch_radius64_radii_fill<M>(t, d_q, perm, nq, d_r, d_offsets, d_out, nullptr, lease)));
+        if (rc == PTK_OK && sort) rc = sort_rows64(nq, d_offsets, d_out);
+        return rc;
+      });
 }
 
 // ---- the radius searches of the tree's own points (ptk.h) ----
@@ -1435,8 +1395,8 @@ int ptk_search64_count_within_self(const ptk_tree64* t, double radius, const dou
 // ptk_search_radius_self in double: the count (max_count = 0), the scan and the fill on the device.
 int ptk_search64_radius_self(const ptk_tree64* t, double radius, const double* radii, int sort, uint64_t* offsets,
                              ptk_neighbor64** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_radius_self(t, radius, radii, /*host_values=*/true, offsets, "search_radius_self",
                              "kd_tree::search_radius_self, one point at a time");
   if (rc != PTK_OK) return rc;
@@ -1452,50 +1412,27 @@ int ptk_search64_radius_self(const ptk_tree64* t, double radius, const double* r
   double* d_r = reinterpret_cast<double*>(bin.p);
   uint64_t* d_c = reinterpret_cast<uint64_t*>(bin.p + c_room);
   uint64_t* d_o = reinterpret_cast<uint64_t*>(bin.p + 2 * c_room);
-  if (he == hipSuccess) he = hipMemset(d_c, 0, (np + 1) * 8);
   if (he == hipSuccess && radii != nullptr) he = hipMemcpy(d_r, radii, np * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    const double* d_radii = radii != nullptr ? d_r : nullptr;
-    rc = ptk_search64_count_within_self_device(t, radius, d_radii, 0, d_c, nullptr);
-    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, np, offsets);
-    if (rc == PTK_OK) {
-      const size_t obytes = std::max<uint64_t>(offsets[np], 1) * sizeof(ptk_neighbor64);
-      he = bout.get(t, 1, obytes);
-      ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(bout.p);
-      if (he == hipSuccess) {
+  const double* d_radii = radii != nullptr ? d_r : nullptr;
+  return rows_to_host(
+      he, np, d_c, d_o, offsets, out, rows_in<ptk_neighbor64>(t, bout),
+      [&](uint64_t* d_counts) { return ptk_search64_count_within_self_device(t, radius, d_radii, 0, d_counts, nullptr); },
+      [&](const uint64_t* d_offsets, ptk_neighbor64* d_rows, uint64_t) {
+        ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(d_rows);
         Stack64Lease lease(t, nullptr);
-        rc = lease.acquire(np);
+        int rc = lease.acquire(np);
         for (uint64_t first = 0; first < np && rc == PTK_OK; first += lease.piece)
           rc = ptkf::radius64_self_fill(t->dev, t->metric.load(), first, std::min<uint64_t>(lease.piece, np - first), radius,
-                                        d_radii, d_o, d_out, lease.stack, t->slots, nullptr);
-        if (rc == PTK_OK && sort) {
-          hipLaunchKernelGGL(ptk::sort_rows64_kernel, dim3((uint32_t)((np + ptk::kBlock - 1) / ptk::kBlock)), dim3(ptk::kBlock),
-                             0, nullptr, d_o, np, d_out);
-          he = hipGetLastError();
-        }
-      }
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<ptk_neighbor64*>(std::malloc(obytes));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else {
-          he = hipMemcpy(*out, bout.p, obytes, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+                                        d_radii, d_offsets, d_out, lease.stack, t->slots, nullptr);
+        if (rc == PTK_OK && sort) rc = sort_rows64(np, d_offsets, d_out);
+        return rc;
+      });
 }
 
 int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs, uint64_t nb, uint64_t* offsets,
                      int32_t** out) {
+  if (out != nullptr) *out = nullptr;
   if (out == nullptr || offsets == nullptr) return fail(PTK_ERR_INVALID, "null output pointer");
-  *out = nullptr;
   int rc = check_search(t, mins, nb);
   if (rc != PTK_OK) return rc;
   if (nb > 0 && maxs == nullptr) return fail(PTK_ERR_INVALID, "null box buffer");
@@ -1509,36 +1446,19 @@ int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs
   if (he == hipSuccess) he = mx.alloc(bbytes);
   if (he == hipSuccess) he = counts.alloc((nb + 1) * 8);
   if (he == hipSuccess) he = offs.alloc((nb + 1) * 8);
-  if (he == hipSuccess) he = hipMemset(counts.p, 0, (nb + 1) * 8);
   if (he == hipSuccess) he = hipMemcpy(mn.p, mins, bbytes, hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(mx.p, maxs, bbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess) {
-    const double *d_mn = mn.as<double>(), *d_mx = mx.as<double>();
-    uint64_t *d_c = counts.as<uint64_t>(), *d_o = offs.as<uint64_t>();
-    Stack64Lease lease(t, nullptr);
-    rc = lease.acquire(nb);
-    if (rc == PTK_OK) rc = launch_box64<false>(t, d_mn, d_mx, nb, d_c, nullptr, nullptr, nullptr, lease);
-    if (rc == PTK_OK) rc = scan_counts64(d_c, d_o, nb, offsets);
-    if (rc == PTK_OK) {
-      const size_t obytes = std::max<uint64_t>(offsets[nb], 1) * sizeof(int32_t);
-      he = rows.alloc(obytes);
-      if (he == hipSuccess) rc = launch_box64<true>(t, d_mn, d_mx, nb, nullptr, d_o, rows.as<int32_t>(), nullptr, lease);
-      if (he == hipSuccess && rc == PTK_OK) {
-        *out = static_cast<int32_t*>(std::malloc(obytes));
-        if (*out == nullptr) {
-          rc = fail(PTK_ERR_NOMEM, "out of memory");
-        } else {
-          he = hipMemcpy(*out, rows.p, obytes, hipMemcpyDeviceToHost);
-        }
-      }
-    }
-  }
-  if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (rc != PTK_OK && *out) {
-    std::free(*out);
-    *out = nullptr;
-  }
-  return rc;
+  const double *d_mn = mn.as<double>(), *d_mx = mx.as<double>();
+  Stack64Lease lease(t, nullptr);  // (one lease over both passes)
+  return rows_to_host(
+      he, nb, counts.as<uint64_t>(), offs.as<uint64_t>(), offsets, out, rows_in<int32_t>(rows),
+      [&](uint64_t* d_counts) {
+        const int rc = lease.acquire(nb);
+        return rc != PTK_OK ? rc : launch_box64<false>(t, d_mn, d_mx, nb, d_counts, nullptr, nullptr, nullptr, lease);
+      },
+      [&](const uint64_t* d_offsets, int32_t* d_rows, uint64_t) {
+        return launch_box64<true>(t, d_mn, d_mx, nb, nullptr, d_offsets, d_rows, nullptr, lease);
+      });
 }
 
 }  // extern "C"
