@@ -765,6 +765,16 @@ int ptk_debug_batch_permutation(const ptk_tree* tree, const float* d_queries, ui
 /* Where the creation of this handle went, in ms: [0] host build of the tree (ptk_tree_create_from_points only),
  * [1] re-encoding for the device and stream checks, [2] upload and the point gather on the device. */
 int ptk_debug_create_phases(const ptk_tree* tree, double ms[3]);
+/* How the tree of this handle was built: counts[0] = 1 when the partitions of its top levels were made on the device
+ * (ptk_tree_create_from_points with 2^18 points or more on a handle with a device), else 0 and *why (a static string,
+ * empty otherwise) says what sent the build to the host: "fewer than 2^18 points", "PTK_DEVICE_BUILD=0", "host-only
+ * handle", "not built from points" (the stream and descriptor creators), or what the device build stopped at -- a shape
+ * it does not take, more than 64 sliding planes in the top levels, the text of a HIP error.  [1] = nodes of more points
+ * than this were split on the device, [2] = levels partitioned there, [3] = branches of the top, [4] = subtrees the
+ * host's workers built below it, [5] = planes that slid (std::nth_element), [6] = rounds of that call's introselect made
+ * on the device, over all slides, [7] = slides whose whole range went to the host's std::nth_element instead.  After a
+ * build that went to the host [1] .. [7] say how far the device build had come. */
+int ptk_debug_create_route(const ptk_tree* tree, uint64_t counts[8], const char** why);
 /* How a batch of nq queries would be ordered on the device: bits[a] = bits of the Morton key spent on axis a (the
  * first three axes; in proportion to how often a root-to-leaf path of this tree splits on each).  Works on handles
  * without a device replica too. */

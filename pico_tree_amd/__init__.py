@@ -186,6 +186,7 @@ _SIGNATURES = {
     "ptk_debug_piles": (c_int, [c_void_p, POINTER(ctypes.c_uint64)]),
     "ptk_debug_batch_permutation": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p]),
     "ptk_debug_create_phases": (c_int, [c_void_p, POINTER(c_double)]),
+    "ptk_debug_create_route": (c_int, [c_void_p, POINTER(ctypes.c_uint64), POINTER(ctypes.c_char_p)]),
     "ptk_debug_key_bits": (c_int, [c_void_p, c_uint64, POINTER(c_uint32)]),
     "ptk_debug_batch_order": (c_int, [c_void_p, POINTER(c_int)]),
     "ptk_debug_deep_pieces": (c_int, [c_void_p, POINTER(c_uint32)]),
@@ -753,6 +754,20 @@ class KdTree:
         ms = (c_double * 3)()
         _check(_load().ptk_debug_create_phases(self._h, ms))
         return {"host_build_s": ms[0] / 1e3, "encode_s": ms[1] / 1e3, "upload_s": ms[2] / 1e3}
+
+    def create_route(self) -> dict:
+        """How the tree of the handle was built (``ptk_debug_create_route``): ``on_device`` = 1 when the partitions of
+        the top levels were made on the device, else ``why`` names what sent the build to the host; the counters of
+        the device build (levels, branches of the top, subtrees below it, planes that slid and where)."""
+        self._float32_only("create_route()")
+        c = (ctypes.c_uint64 * 8)()
+        why = ctypes.c_char_p()
+        _check(_load().ptk_debug_create_route(self._h, c, byref(why)))
+        names = ("on_device", "threshold", "levels", "top_branches", "subtrees", "slides", "slide_rounds_device",
+                 "slides_host_whole")
+        route = {name: int(v) for name, v in zip(names, c)}
+        route["why"] = (why.value or b"").decode("utf-8", "replace")
+        return route
 
     def knn1_counts(self) -> dict:
         """Counters of the last two-phase k = 1 search (``ptk_debug_knn1_counts``)."""

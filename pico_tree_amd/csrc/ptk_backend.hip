@@ -1119,15 +1119,20 @@ int ptk_tree_create_from_points(const float* points, uint64_t n_points, uint32_t
     // below by the host's workers -- the same tree.  PTK_DEVICE_BUILD=0: everything on the host.
     internal::flat_tree<int, float, dynamic_extent> flat(dim);
     bool built = false;
+    ptk::BuildRoute& route = t->create_route;
+    route.why = device == kDeviceNone                 ? "host-only handle"
+                : n_points < (1ull << 18)             ? "fewer than 2^18 points"
+                : env_int("PTK_DEVICE_BUILD", 1) == 0 ? "PTK_DEVICE_BUILD=0"
+                                                      : "no usable HIP device";
     if (device != kDeviceNone && n_points >= (1ull << 18) && env_int("PTK_DEVICE_BUILD", 1) != 0) {
       int count = 0, dev = device;
       if (hipGetDeviceCount(&count) == hipSuccess && count > 0 && (dev >= 0 || hipGetDevice(&dev) == hipSuccess) && dev < count) {
         DeviceGuard guard(dev);
         g_warmup.wait(dev);
         double ms[2] = {0, 0};
-        const char* why = "hipSetDevice failed";
-        if (guard.ok) built = ptk::device_top_build(points, n_points, dim, (size_t)max_leaf_size, build_threads(), view, flat, ms, &why);
-        if (!built && clock.on) std::fprintf(stderr, "[ptk create] top levels not on the device: %s\n", why);
+        route.why = "hipSetDevice failed";
+        if (guard.ok) built = ptk::device_top_build(points, n_points, dim, (size_t)max_leaf_size, build_threads(), view, flat, ms, &route);
+        if (!built && clock.on) std::fprintf(stderr, "[ptk create] top levels not on the device: %s\n", route.why);
         if (built && clock.on)
           std::fprintf(stderr, "[ptk create] top levels on the device     %8.2f ms\n[ptk create] subtrees on the host          %8.2f ms\n",
                        ms[0], ms[1]);
@@ -2694,6 +2699,16 @@ int ptk_debug_piles(const ptk_tree* t, uint64_t out[3]) {
 int ptk_debug_create_phases(const ptk_tree* t, double ms[3]) {
   if (t == nullptr || ms == nullptr) return fail(PTK_ERR_INVALID, "null argument");
   for (int i = 0; i < 3; ++i) ms[i] = t->create_ms[i];
+  return PTK_OK;
+}
+
+int ptk_debug_create_route(const ptk_tree* t, uint64_t counts[8], const char** why) {
+  if (t == nullptr || counts == nullptr || why == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  const ptk::BuildRoute& r = t->create_route;
+  const uint64_t c[8] = {(uint64_t)r.on_device, r.threshold, r.levels, r.top_branches, r.subtrees, r.slides, r.slide_rounds_device,
+                         r.slides_host_whole};
+  std::memcpy(counts, c, sizeof(c));
+  *why = r.why;
   return PTK_OK;
 }
 

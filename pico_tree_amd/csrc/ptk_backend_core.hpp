@@ -184,6 +184,22 @@ struct HostIo {
 }  // namespace ptkb
 using namespace ptkb;
 
+namespace ptk {
+// How the tree of a handle was built (ptk_debug_create_route): filled by device_top_build (ptk_build.hpp) and kept by
+// the handle.  `why` is a static string: empty when the top levels came from the device, else what sent the build to
+// the host; the counters then say how far the device build had come.
+struct BuildRoute {
+  int on_device = 0;
+  const char* why = "not built from points";
+  uint64_t threshold = 0;            // nodes of more points than this were split on the device
+  uint64_t levels = 0;               // calls of the level partitioner
+  uint64_t top_branches = 0, subtrees = 0;  // branches of the top, frontier ranges below it
+  uint64_t slides = 0;               // calls of the slide callback
+  uint64_t slide_rounds_device = 0;  // iterations of the device introselect loop, over all slides
+  uint64_t slides_host_whole = 0;    // slides that took the keyed std::nth_element path
+};
+}  // namespace ptk
+
 struct ptk_tree {
   // host copy of the flat tree (DFS stream as handed in / built)
   uint32_t dim = 0;
@@ -203,6 +219,7 @@ struct ptk_tree {
   uint64_t n_leaves = 0;
   uint32_t max_leaf_count = 0;
   double create_ms[3] = {0, 0, 0};  // host build | re-encoding + checks | upload + point gather (ptk_debug_create_phases)
+  ptk::BuildRoute create_route;     // ptk_debug_create_route
 
   // device replica
   int device = kDeviceNone;

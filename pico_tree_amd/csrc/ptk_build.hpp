@@ -20,7 +20,9 @@
 // (build_flat_tree_below()).  A node whose partition leaves one side empty needs the sliding step, std::nth_element,
 // whose permutation only the host library defines: its range makes a round trip to the host (on the scan-like cloud of
 // BASELINE config 2 an outlier makes the plane of a 963 k-point node slide four times in a row).
-// tests/test_gpu_parity.py compares the stream of a tree built this way with the host build byte for byte.
+// tests/test_device_build.py compares a tree built this way with the host build byte for byte -- and, by the record of
+// ptk_debug_create_route (BuildRoute), that it WAS built this way; tests/cpp/emulate_build_main.cpp runs the kernels of
+// ptk_kernels_build.hpp on the CPU against std::partition and std::nth_element.
 
 #pragma once
 
@@ -40,219 +42,9 @@
 #include <vector>
 
 #include "pico_tree/internal/flat_tree.hpp"
-
-// A kernel that is not a template is defined in a header several translation units include (ptk_backend_core.hpp):
-// internal linkage, so every unit that launches it has its own and the units that do not emit nothing.
-#ifndef PTK_GLOBAL
-#define PTK_GLOBAL static __global__
-#endif
-
+#include "ptk_kernels_build.hpp"
 
 namespace ptk {
-
-struct BuildSeg {
-  uint32_t begin, end, axis;
-  float plane;
-  uint32_t m;          // out: points below the plane
-  uint32_t pass_left;  // out: of those, already among the first m positions
-  uint32_t pad0, pad1;
-};
-
-constexpr uint32_t kBuildMaxDim = 8;
-constexpr uint32_t kBuildBoxBlocks = 1024;
-
-PTK_GLOBAL __launch_bounds__(256) void build_iota_kernel(int32_t* __restrict__ idx, uint32_t n) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) idx[i] = (int32_t)i;
-}
-
-// Per block: min and max of every coordinate over a slice of the points (exact: any grouping gives the same box).
-PTK_GLOBAL __launch_bounds__(256) void build_box_kernel(
-    const float* __restrict__ pts, uint32_t n, uint32_t dim, float* __restrict__ partial) {
-  __shared__ float lo[256], hi[256];
-  for (uint32_t a = 0; a < dim; ++a) {
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
-      const float v = pts[i * dim + a];
-      mn = v < mn ? v : mn;
-      mx = v > mx ? v : mx;
-    }
-    lo[threadIdx.x] = mn;
-    hi[threadIdx.x] = mx;
-    __syncthreads();
-    for (uint32_t s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s) {
-        lo[threadIdx.x] = lo[threadIdx.x + s] < lo[threadIdx.x] ? lo[threadIdx.x + s] : lo[threadIdx.x];
-        hi[threadIdx.x] = hi[threadIdx.x + s] > hi[threadIdx.x] ? hi[threadIdx.x + s] : hi[threadIdx.x];
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      partial[(blockIdx.x * dim + a) * 2 + 0] = lo[0];
-      partial[(blockIdx.x * dim + a) * 2 + 1] = hi[0];
-    }
-    __syncthreads();
-  }
-}
-
-// The node of the level position i lies in (the nodes are in position order); nsegs if none.
-__device__ __forceinline__ uint32_t build_find(const BuildSeg* __restrict__ segs, uint32_t nsegs, uint32_t i) {
-  uint32_t lo = 0, hi = nsegs;  // first node with begin > i
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (segs[mid].begin <= i) lo = mid + 1;
-    else hi = mid;
-  }
-  if (lo == 0) return nsegs;
-  return i < segs[lo - 1].end ? lo - 1 : nsegs;
-}
-
-PTK_GLOBAL __launch_bounds__(256) void build_flag_kernel(
-    const float* __restrict__ pts, uint32_t dim, const int32_t* __restrict__ idx, const BuildSeg* __restrict__ segs,
-    uint32_t nsegs, uint32_t n, uint32_t* __restrict__ flags) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i > n) return;
-  uint32_t f = 0;
-  if (i < n) {
-    const uint32_t s = build_find(segs, nsegs, i);
-    if (s < nsegs) f = pts[(uint64_t)(uint32_t)idx[i] * dim + segs[s].axis] < segs[s].plane ? 1u : 0u;
-  }
-  flags[i] = f;  // (flags[n] = 0: the scan then also yields the total)
-}
-
-PTK_GLOBAL void build_cut_kernel(const uint32_t* __restrict__ sums, BuildSeg* __restrict__ segs, uint32_t nsegs) {
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nsegs) return;
-  const uint32_t b = segs[s].begin;
-  const uint32_t m = sums[segs[s].end] - sums[b];
-  segs[s].m = m;
-  segs[s].pass_left = sums[b + m] - sums[b];
-}
-
-PTK_GLOBAL __launch_bounds__(256) void build_list_kernel(
-    const uint32_t* __restrict__ flags, const uint32_t* __restrict__ sums, const BuildSeg* __restrict__ segs,
-    uint32_t nsegs, uint32_t n, uint32_t* __restrict__ from_left, uint32_t* __restrict__ from_right) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t s = build_find(segs, nsegs, i);
-  if (s >= nsegs) return;
-  const uint32_t b = segs[s].begin, m = segs[s].m;
-  const uint32_t before = sums[i] - sums[b];  // passing positions of this node before i
-  if (i < b + m) {
-    if (!flags[i]) from_left[b + (i - b) - before] = i;  // its rank among the failing positions of the left part
-  } else if (flags[i]) {
-    from_right[b + before - segs[s].pass_left] = i;  // its rank among the passing positions of the right part
-  }
-}
-
-PTK_GLOBAL __launch_bounds__(256) void build_swap_kernel(
-    int32_t* __restrict__ idx, const BuildSeg* __restrict__ segs, uint32_t nsegs, uint32_t n,
-    const uint32_t* __restrict__ from_left, const uint32_t* __restrict__ from_right) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t s = build_find(segs, nsegs, i);
-  if (s >= nsegs) return;
-  const uint32_t b = segs[s].begin, swaps = segs[s].m - segs[s].pass_left, k = i - b;
-  if (k >= swaps) return;
-  const uint32_t l = from_left[b + k], r = from_right[b + swaps - 1u - k];
-  const int32_t t = idx[l];
-  idx[l] = idx[r];
-  idx[r] = t;
-}
-
-// ---- the sliding step (std::nth_element) ---------------------------------------------------------------------------
-// When a partition leaves one side empty the reference slides the plane to the nearest point with std::nth_element
-// (internal/kd_tree_builder.hpp:255-275), and the permutation that call leaves is part of the tree.  libstdc++'s
-// nth_element is an introselect (bits/stl_algo.h:1964-1986): rounds of "median of three to the front, Hoare partition
-// of the rest around it, keep the side that holds nth" until at most three elements are left.  The first rounds --
-// the ones that touch a million indices -- are made here; the partition of a round is, like std::partition above,
-// a pairing by rank:
-//
-//   __unguarded_partition(first + 1, last, pivot = first) moves a left pointer up to the next element that is NOT
-//   below the pivot and a right pointer down to the next that is NOT above it, swaps the two and goes on, until the
-//   pointers meet; until then both pointers only see elements nobody has moved yet.  So the k-th "left stop"
-//   (positions with !(v < pivot), ascending) is swapped with the k-th "right stop" (positions with !(pivot < v),
-//   descending) for every k below K = the first k whose left stop is not left of its right stop; the function returns
-//   where the left pointer stands at the end (slide_pair_kernel).
-//
-// flags (both kinds, packed in one 64-bit word), one scan, the two rank lists, the pairs; the host reads the cut and
-// decides which side is kept, exactly as __introselect does.  Once the range is small the host finishes the SAME
-// call -- std::__introselect on what is left, with what is left of its depth limit -- so the outcome is libstdc++'s
-// to the last swap (tests/test_device_build.py: byte-identical trees on clouds whose planes slide).
-PTK_GLOBAL void slide_pivot_kernel(const float* __restrict__ pts, uint32_t dim, uint32_t axis, int32_t* __restrict__ idx,
-                                   uint32_t first, uint32_t last, float* __restrict__ pivot) {
-  // __move_median_to_first(result = first, a = first + 1, b = mid, c = last - 1)
-  const uint32_t a = first + 1u, b = first + (last - first) / 2u, c = last - 1u;
-  auto val = [&](uint32_t i) { return pts[(uint64_t)(uint32_t)idx[i] * dim + axis]; };
-  const float va = val(a), vb = val(b), vc = val(c);
-  uint32_t pick;
-  if (va < vb) {
-    if (vb < vc) pick = b;
-    else if (va < vc) pick = c;
-    else pick = a;
-  } else if (va < vc) {
-    pick = a;
-  } else if (vb < vc) {
-    pick = c;
-  } else {
-    pick = b;
-  }
-  const int32_t t = idx[first];
-  idx[first] = idx[pick];
-  idx[pick] = t;
-  *pivot = val(first);
-}
-
-// flags[i - lo] = {left stop, right stop << 32} for the positions [lo, hi); flags[hi - lo] = 0 (the scan's total).
-PTK_GLOBAL __launch_bounds__(256) void slide_flag_kernel(const float* __restrict__ pts, uint32_t dim, uint32_t axis,
-                                                         const int32_t* __restrict__ idx, uint32_t lo, uint32_t hi,
-                                                         const float* __restrict__ pivot,
-                                                         unsigned long long* __restrict__ flags) {
-  const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
-  if (i > hi) return;
-  unsigned long long f = 0ull;
-  if (i < hi) {
-    const float v = pts[(uint64_t)(uint32_t)idx[i] * dim + axis], p = *pivot;
-    f = (!(v < p) ? 1ull : 0ull) | (!(p < v) ? 1ull << 32 : 0ull);
-  }
-  flags[i - lo] = f;
-}
-
-// left_list[k] = position of the k-th left stop (ascending), right_list[k] = position of the k-th right stop (descending).
-PTK_GLOBAL __launch_bounds__(256) void slide_list_kernel(const unsigned long long* __restrict__ flags,
-                                                         const unsigned long long* __restrict__ sums, uint32_t lo,
-                                                         uint32_t hi, uint32_t* __restrict__ left_list,
-                                                         uint32_t* __restrict__ right_list) {
-  const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
-  if (i >= hi) return;
-  const unsigned long long f = flags[i - lo], before = sums[i - lo], total = sums[hi - lo];
-  if (f & 0xFFFFFFFFull) left_list[(uint32_t)before] = i;
-  if (f >> 32) right_list[(uint32_t)(total >> 32) - (uint32_t)(before >> 32) - 1u] = i;
-}
-
-// The pairs below K are swapped (K = the first k whose left stop is missing or not left of its right stop).  What
-// the function returns is where the left pointer stands then: it has moved on from left stop K - 1 to the next element
-// that is not below the pivot -- left stop K, unless it first meets the element it swapped into right stop K - 1:
-// *cut = min(left stop K, right stop K - 1)   (K = 0: left stop 0, which a median-of-three pivot guarantees).
-PTK_GLOBAL __launch_bounds__(256) void slide_pair_kernel(int32_t* __restrict__ idx, const unsigned long long* __restrict__ sums,
-                                                         uint32_t n_range, const uint32_t* __restrict__ left_list,
-                                                         const uint32_t* __restrict__ right_list, uint32_t* __restrict__ cut) {
-  const unsigned long long total = sums[n_range];
-  const uint32_t n_left = (uint32_t)total, n_right = (uint32_t)(total >> 32);
-  const uint32_t pairs = n_left < n_right ? n_left : n_right;
-  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-  if (k > pairs) return;
-  const bool active = k < pairs && left_list[k] < right_list[k];
-  if (active) {
-    const uint32_t l = left_list[k], r = right_list[k];
-    const int32_t t = idx[l];
-    idx[l] = idx[r];
-    idx[r] = t;
-  } else if (k == 0u || left_list[k - 1u] < right_list[k - 1u]) {  // k = K
-    const uint32_t l_k = k < n_left ? left_list[k] : 0xFFFFFFFFu;
-    *cut = k == 0u ? l_k : (l_k < right_list[k - 1u] ? l_k : right_list[k - 1u]);
-  }
-}
 
 // Device buffers of one build (freed on every path).
 struct BuildBuffers {
@@ -277,13 +69,16 @@ struct BuildBuffers {
 // Builds the sliding-midpoint tree of `points` with the partitions of the large nodes made on the current device.
 // Returns false (and leaves `tree` alone) when the build has to be made on the host instead: a HIP failure, a
 // plane that slides in the top levels, an unsupported shape.  `top_ms` (optional): time spent in the device levels.
+// `route` (optional): what was done, and why not when the answer is false (ptk_debug_create_route).
 template <typename SpaceView_, typename Tree_>
 bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_leaf_size, unsigned threads,
-                      SpaceView_ const& view, Tree_& tree, double* phase_ms = nullptr, const char** why = nullptr) {
+                      SpaceView_ const& view, Tree_& tree, double* phase_ms = nullptr, BuildRoute* route = nullptr) {
   using namespace pico_tree;
   using box_type = typename Tree_::box_type;
-  const char* unused = nullptr;
-  const char*& reason = why != nullptr ? *why : unused;
+  BuildRoute unused;
+  BuildRoute& did = route != nullptr ? *route : unused;
+  did = BuildRoute{};
+  const char*& reason = did.why;
   reason = "shape not supported";
   if (dim == 0 || dim > kBuildMaxDim || n < 2 || n >= (1ull << 31)) return false;
   const auto t_start = std::chrono::steady_clock::now();
@@ -306,6 +101,7 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
   // Nodes above this many points are split here: about eight subtrees per worker, none smaller than 16 k points.
   const size_t threshold = std::max<size_t>(std::max<size_t>(16384, max_leaf_size), n / ((size_t)std::max(1u, threads) * 8));
   const size_t max_segs = 2 * (n / threshold) + 64;
+  did.threshold = threshold;
   BuildBuffers b;
   size_t scan_bytes = 0;
   if (!ok(rocprim::exclusive_scan(nullptr, scan_bytes, b.flags, b.sums, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(),
@@ -338,6 +134,7 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
 
   std::vector<BuildSeg> host_segs;
   auto on_device = [&](std::vector<internal::top_segment<float>>& segments) -> bool {
+    ++did.levels;
     if (segments.size() > max_segs) {
       reason = "more nodes in a level than planned for";
       return false;
@@ -368,6 +165,7 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
   std::vector<std::pair<float, int>> keyed;
   unsigned n_slides = 0;
   auto slide = [&](internal::top_segment<float>& seg, size_t nth) -> bool {
+    ++did.slides;
     if (++n_slides > 64) {  // (a pile of coincident outliers peels one point per level: the host builder's business)
       reason = "too many sliding planes in the top levels";
       return false;
@@ -403,6 +201,7 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
       uint32_t* d_cut = reinterpret_cast<uint32_t*>(b.pivot) + 1;
       while (last - first > kHostBelow && depth_limit > 0) {
         --depth_limit;
+        ++did.slide_rounds_device;
         const uint32_t lo = (uint32_t)first + 1u, hi = (uint32_t)last, n_range = hi - lo;
         const uint32_t none = 0xFFFFFFFFu;
         if (!ok(hipMemcpyAsync(d_cut, &none, 4, hipMemcpyHostToDevice, nullptr))) return false;
@@ -444,6 +243,7 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
       seg.plane = points[(size_t)slid[nth_pos - first] * dim + axis];
       return ok(hipMemcpy(b.idx + first, slid.data(), count * 4, hipMemcpyHostToDevice));
     }
+    ++did.slides_host_whole;
     const size_t count = seg.end - seg.begin;
     slid.resize(count);
     keyed.resize(count);
@@ -471,6 +271,8 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
   std::vector<std::pair<size_t, size_t>> frontier;
   reason = "a level of the top failed";
   if (!internal::split_top_levels(root, (size_t)n, threshold, on_device, slide, top, frontier)) return false;
+  did.top_branches = top.size();
+  did.subtrees = frontier.size();
   lap("levels (slides included)");
   if (verbose) std::fprintf(stderr, "[ptk build]   %-34s %8.2f ms (%zu top branches, %zu subtrees)\n", "of which slides", slide_ms, top.size(), frontier.size());
   std::vector<int> indices(n);
@@ -485,6 +287,8 @@ bool device_top_build(const float* points, uint64_t n, uint32_t dim, size_t max_
     phase_ms[0] = std::chrono::duration<double, std::milli>(t_top - t_start).count();
     phase_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_top).count();
   }
+  did.on_device = 1;
+  reason = "";
   return true;
 }
 

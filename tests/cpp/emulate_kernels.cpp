@@ -18,10 +18,16 @@ thread_local dim3 blockDim;
 #include <ucontext.h>
 
 #include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <sstream>
 #include <string>
 #include <vector>
+
+// PTK_EMU_SCHEDULERS_ONLY: only the lane, wavefront and block schedulers of this file -- for a unit that brings kernels
+// of its own and needs none of the handles and entry points below (tests/cpp/emulate_build_main.cpp).
+#ifndef PTK_EMU_SCHEDULERS_ONLY
 
 // The record stacks of the kernels (Stack of ptk_kernels.hpp, Stack64 of ptk_kernels_f64.hpp) report the number of
 // records they hold after every push: emu_stack_high_water() below is the largest since the last reset.  Only this
@@ -70,6 +76,8 @@ void emu_set_p2_cap(uint32_t cap) { g_p2_cap = cap; }
 int emu_ovf_class(uint32_t depth, int s_lds) { return ptk::ovf_class_of(depth, s_lds); }
 int emu_ovf_slots(int cls) { return cls >= 0 && cls < ptk::kDeepClass ? ptk::kOvfSlots[cls] : -1; }
 }
+
+#endif  // PTK_EMU_SCHEDULERS_ONLY
 
 // ---- wave-level rendezvous for kernels that use __ballot ---------------------------------
 // The 64 lanes of one wavefront run as 64 cooperative fibers (ucontext) on the calling
@@ -180,6 +188,7 @@ int emu_lane() { return g_block != nullptr ? g_block->current & 63 : g_fibers->c
 
 namespace {
 
+#ifndef PTK_EMU_SCHEDULERS_ONLY
 thread_local std::string g_err;
 
 struct Emu {
@@ -206,9 +215,15 @@ struct Emu {
   ptk::RadiusCapture cap{};
 };
 
+#endif  // PTK_EMU_SCHEDULERS_ONLY
+
 // Kernels whose lanes are independent: every lane of every block, sequentially.
 template <typename F>
+#ifdef PTK_EMU_SCHEDULERS_ONLY
+void for_each_lane(uint64_t nq, F&& f, uint32_t block) {
+#else
 void for_each_lane(uint64_t nq, F&& f, uint32_t block = ptk::kBlock) {
+#endif
   const uint32_t blocks = (uint32_t)((nq + block - 1) / block);
   gridDim.x = blocks;
   blockDim.x = block;
@@ -351,6 +366,7 @@ void for_each_block(uint32_t blocks, uint32_t threads, F&& f) {
   g_block = nullptr;
 }
 
+#ifndef PTK_EMU_SCHEDULERS_ONLY
 // The launch-order query records {x, y, z, bits(row)} phase 1 has to produce (host restatement).
 std::vector<float4> pack(const float* q, uint32_t dim, const uint32_t* perm, uint64_t nq) {
   std::vector<float4> qs(nq ? nq : 1);
@@ -362,7 +378,10 @@ std::vector<float4> pack(const float* q, uint32_t dim, const uint32_t* perm, uin
   return qs;
 }
 
+#endif  // PTK_EMU_SCHEDULERS_ONLY
 }  // namespace
+
+#ifndef PTK_EMU_SCHEDULERS_ONLY
 
 // The launches the backend makes for a metric other than L2 squared: register k-list for k <= 32
 // (k = 1 included -- the two-phase search is L2 only), LDS k-list above, any-dimension kernels.
@@ -1628,3 +1647,5 @@ int emu64_box(void* h, const double* mins, const double* maxs, uint64_t nb, uint
 }
 
 }  // extern "C"
+
+#endif  // PTK_EMU_SCHEDULERS_ONLY

@@ -384,3 +384,27 @@ def test_host_loop_entry_points_equal_the_oracle(metric):
     lib.ptk_free(rows)
     boff, bflat = ref.search_box(lo, hi)
     assert np.array_equal(offsets, boff) and np.array_equal(flat, bflat)
+
+
+def test_create_route_of_handles_without_a_device_build():
+    """ptk_debug_create_route: a handle the device build never saw says why (tests/test_device_build.py has the
+    handles it did see)."""
+    from ctypes import byref, c_char_p, c_uint64, c_void_p
+
+    lib = pt._load()
+    pts = ds.uniform_cloud(3_000, 3, 4)
+    tree = pt.KdTree(pts, pt.Metric.L2Squared, 9, device=pt.PTK_DEVICE_NONE)
+    assert tree.create_route() == {"on_device": 0, "why": "host-only handle", "threshold": 0, "levels": 0, "top_branches": 0,
+                                   "subtrees": 0, "slides": 0, "slide_rounds_device": 0, "slides_host_whole": 0}
+    stream = tree._serialize()
+    h = c_void_p()
+    assert lib.ptk_tree_create_from_stream(pts.ctypes.data, len(pts), 3, stream, len(stream), pt.PTK_DEVICE_NONE, byref(h)) == 0
+    counts, why = (c_uint64 * 8)(*([7] * 8)), c_char_p()
+    assert lib.ptk_debug_create_route(h, counts, byref(why)) == 0
+    assert list(counts) == [0] * 8 and why.value == b"not built from points"
+    assert lib.ptk_debug_create_route(None, counts, byref(why)) == -1
+    assert lib.ptk_debug_create_route(h, None, byref(why)) == -1
+    assert lib.ptk_debug_create_route(h, counts, None) == -1
+    lib.ptk_tree_destroy(h)
+    with pytest.raises(pt.PtkError):  # float32 only, like create_phases()
+        pt.KdTree(pts.astype(np.float64), pt.Metric.L2Squared, 9, device=pt.PTK_DEVICE_NONE).create_route()
