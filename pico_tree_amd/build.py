@@ -99,6 +99,23 @@ def _unit_stale(unit: str, flags_line: str) -> bool:
     return recorded == "" or recorded != _signature(unit, flags_line)
 
 
+def _library_current(lib: str, flags_line: str) -> bool:
+    """The library is there and was linked from objects whose recorded signatures are those of the sources as they are
+    now -- whether the objects themselves are still there or not (a copy of the tree may leave them behind: nothing is
+    compiled again for that)."""
+    linked = os.path.join(OBJ, os.path.basename(lib) + ".sig")
+    if not (os.path.exists(lib) and os.path.exists(linked)):
+        return False
+    sigs = []
+    for unit in UNITS:
+        sig = _signature(unit, flags_line)
+        if sig == "":
+            return False
+        sigs.append(sig)
+    with open(linked) as f:
+        return f.read() == "\n".join(sigs)
+
+
 def _compile(unit: str, flags: list, flags_line: str, verbose: bool) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     obj = os.path.join(OBJ, unit + ".o")
@@ -116,6 +133,8 @@ def build(force: bool = False, verbose: bool = False, lib: str = LIB) -> str:
     flags = _compile_flags()
     flags_line = " ".join(flags)
     os.makedirs(OBJ, exist_ok=True)
+    if not force and _library_current(lib, flags_line):
+        return lib
     todo = [u for u in UNITS if force or _unit_stale(u, flags_line)]
     if todo:
         jobs = max(1, min(len(todo), int(os.environ.get("PTK_BUILD_JOBS", os.cpu_count() or 4))))

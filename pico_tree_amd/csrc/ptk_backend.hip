@@ -444,6 +444,14 @@ bool block_sort(uint64_t nq) {
   const int mode = knob_int("sort_block", -1);
   return mode < 0 ? nq >= (3ull << 18) : mode != 0 && nq >= ptk::kSortTile;
 }
+// The block form on narrow streams (ptk_sort.hpp, batch_order_narrow): the default wherever the block form is; a forced
+// sort_block keeps the passes of r04 unless sort_narrow asks too.  Test hook sort_narrow: 0 = the r04 passes, 1 = the
+// digit stream, + 2 = packed items into the last pass, + 4 = the key kernel's rows through LDS.
+uint32_t narrow_sort(uint64_t nq) {
+  if (!block_sort(nq)) return 0u;
+  const int mode = knob_int("sort_narrow", knob_int("sort_block", -1) < 0 ? 7 : 0);
+  return mode > 0 ? (uint32_t)mode | 1u : 0u;
+}
 bool own_sort(uint64_t nq) {
   if (nq >= (1ull << 31)) return false;
   return knob_int("sort", 1) != 0;
@@ -527,6 +535,55 @@ int make_permutation(const ptk_tree* t, const float* d_q, uint64_t nq, hipStream
     const uint3 b3 = make_uint3(b[0], b[1], b[2]);
     const int passes = (bits + 7) / 8;
     const size_t smem = ptk::kRadixBins * 4;
+    if (const uint32_t narrow = narrow_sort(nq)) {
+      // The same launches on narrow streams: keys -> pairs [-> packed words] -> permutation, and beside every item its
+      // next digit as a byte (in keys_out, which only the rocprim path sorts into) for the next histogram.
+      uint8_t* digits = reinterpret_cast<uint8_t*>(keys_out);
+      const bool staged = (narrow & 4u) != 0u && t->dim == 3 && (reinterpret_cast<uintptr_t>(d_q) & 15u) == 0u;
+      const bool pack = (narrow & 2u) != 0u && nq <= (1ull << ptk::kPackedRowBits);
+      const void* from = keys;
+      uint32_t from_kind = ptk::kItemKeys;
+      for (int p = 0; p < passes; ++p) {
+        const uint32_t shift = 8u * (uint32_t)p;
+        const bool last = p + 1 == passes;
+        void* to = last ? (void*)ids_out : from == pairs_a ? (void*)pairs_b : (void*)pairs_a;
+        const uint32_t to_kind = last ? ptk::kItemRows : pack && bits - 8 * (p + 1) <= 8 ? ptk::kItemPacked : ptk::kItemPairs;
+        if (p > 0)
+          hipLaunchKernelGGL((ptk::radix_digit_hist_kernel<>), dim3(tiles), dim3(ptk::kSortBlock), smem, s, digits,
+                             (uint32_t)nq, stride, hist, as_given);
+        else if (staged)
+          hipLaunchKernelGGL((ptk::radix_key_hist_kernel<true>), dim3(tiles), dim3(ptk::kSortBlock), ptk::kSortKeyStagedLds,
+                             s, d_q, t->dim, (uint32_t)nq, lo3, inv3, b3, keys, shift, stride, hist, cells, as_given);
+        else
+          hipLaunchKernelGGL((ptk::radix_key_hist_kernel<false>), dim3(tiles), dim3(ptk::kSortBlock), ptk::kSortKeyLds, s,
+                             d_q, t->dim, (uint32_t)nq, lo3, inv3, b3, keys, shift, stride, hist, cells, as_given);
+        hipLaunchKernelGGL(ptk::radix_scan_kernel, dim3(ptk::kRadixBins), dim3(64), 0, s, hist, tiles, stride, totals);
+#define PTK_NARROW(IN, OUT)                                                                                            \
+  case (IN) * 4u + (OUT):                                                                                              \
+    hipLaunchKernelGGL((ptk::radix_narrow_scatter_kernel<IN, OUT>), dim3(tiles), dim3(ptk::kSortBlock),                \
+                       ptk::kSortScatterLds, s, from, to, last ? nullptr : digits, (uint32_t)nq, shift, stride, hist,  \
+                       totals, as_given);                                                                              \
+    break
+        switch (from_kind * 4u + to_kind) {
+          PTK_NARROW(ptk::kItemKeys, ptk::kItemPairs);
+          PTK_NARROW(ptk::kItemKeys, ptk::kItemPacked);
+          PTK_NARROW(ptk::kItemKeys, ptk::kItemRows);
+          PTK_NARROW(ptk::kItemPairs, ptk::kItemPairs);
+          PTK_NARROW(ptk::kItemPairs, ptk::kItemPacked);
+          PTK_NARROW(ptk::kItemPairs, ptk::kItemRows);
+          PTK_NARROW(ptk::kItemPacked, ptk::kItemRows);
+          default: return fail(PTK_ERR_UNSUPPORTED, "batch order: no scatter for this pair of item layouts");
+        }
+#undef PTK_NARROW
+        from = to;
+        from_kind = to_kind;
+      }
+      PTK_HIP(hipGetLastError());
+      *perm = ids_out;
+      scratch.note_order(1);
+      timer.stop(1, 0);
+      return PTK_OK;
+    }
     const uint2* in = nullptr;
     for (int p = 0; p < passes; ++p) {
       const uint32_t shift = 8u * (uint32_t)p;
