@@ -214,6 +214,9 @@ struct ptk_api<float> {
   static int count_within_self(tree const* t, float radius, float const* radii, std::uint64_t max_count, std::uint64_t* counts) {
     return ptk_search_count_within_self(t, radius, radii, max_count, counts);
   }
+  static int cluster_within_self(tree const* t, float radius, float const* radii, std::uint64_t min_neighbors, std::int32_t* labels) {
+    return ptk_cluster_within_self(t, radius, radii, min_neighbors, labels, nullptr);
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }
@@ -257,6 +260,9 @@ struct ptk_api<double> {
   static int knn_self(tree const* t, std::uint32_t k, neighbor* out) { return ptk_search64_knn_self(t, k, out); }
   static int count_within_self(tree const* t, double radius, double const* radii, std::uint64_t max_count, std::uint64_t* counts) {
     return ptk_search64_count_within_self(t, radius, radii, max_count, counts);
+  }
+  static int cluster_within_self(tree const* t, double radius, double const* radii, std::uint64_t min_neighbors, std::int32_t* labels) {
+    return ptk_search64_cluster_within_self(t, radius, radii, min_neighbors, labels, nullptr);
   }
   static int radius_self(tree const* t, double radius, double const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search64_radius_self(t, radius, radii, sort, offsets, out);

@@ -32,6 +32,7 @@
 #include "core.hpp"
 #include "internal/access.hpp"
 #include "internal/backend.hpp"
+#include "internal/cluster.hpp"
 #include "internal/flat_search.hpp"
 #include "internal/flat_tree.hpp"
 #include "internal/stream.hpp"
@@ -415,6 +416,26 @@ class kd_tree {
       std::vector<scalar_type> const& radii, size_type* counts, size_type const max_count = 0) const {
     check_radii(radii, view().size());
     batched_count_within_self(scalar_type(0), radii.data(), counts, max_count);
+  }
+
+  //! The clusters of the tree's points: the connected components of the
+  //! fixed-radius graph, with DBSCAN's core-point rule.  With row i being
+  //! search_radius_self's row i: point i is core iff that row has at least
+  //! \p min_neighbors entries (0: every point); core points i and j are joined
+  //! whenever j is in row i or i in row j.  labels (size() entries): a core
+  //! point gets the smallest index among the core points of its component, a
+  //! non-core point the smallest label among the core points of its own row,
+  //! -1 (noise) without one.  Served by the backend (ptk_cluster_within_self);
+  //! where it refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined, by the per-point member plus a union-find.
+  inline void cluster_within_self(scalar_type const radius, std::int32_t* labels, size_type const min_neighbors = 0) const {
+    batched_cluster_within_self(radius, nullptr, labels, min_neighbors);
+  }
+
+  inline void cluster_within_self(
+      std::vector<scalar_type> const& radii, std::int32_t* labels, size_type const min_neighbors = 0) const {
+    check_radii(radii, view().size());
+    batched_cluster_within_self(scalar_type(0), radii.data(), labels, min_neighbors);
   }
 
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
@@ -830,6 +851,32 @@ class kd_tree {
           api::count_within_self(device(), radius, radii, static_cast<std::uint64_t>(max_count), c.data()),
           "ptk_search_count_within_self");
       std::copy(c.begin(), c.end(), counts);
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  void batched_cluster_within_self(
+      scalar_type radius, scalar_type const* radii, std::int32_t* labels, size_type min_neighbors) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    size_type const n = view().size();
+    auto const rows_loop = [&]() {
+      std::vector<std::vector<neighbor_type>> rows(n);
+      internal::host_rows_loop(n, [&](size_type i) {
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, rows[i]);
+      });
+      internal::cluster_rows(rows, static_cast<std::uint64_t>(min_neighbors), labels);
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(
+          api::cluster_within_self(device(), radius, radii, static_cast<std::uint64_t>(min_neighbors), labels),
+          "ptk_cluster_within_self");
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

@@ -448,6 +448,41 @@ int ptk_search_radius_self(const ptk_tree* tree, float radius, const float* radi
 int ptk_search_radius_self_fill_device(const ptk_tree* tree, float radius, const float* d_radii, const uint64_t* d_offsets,
                                        ptk_neighbor* d_out, int sort, void* stream);
 
+/* ---- cluster_within_self: the clusters of a tree's own points ------------------------------------------------------
+ * The connected components of the fixed-radius graph over the tree's points -- Euclidean cluster extraction -- with
+ * DBSCAN's core-point rule when min_neighbors > 0.  No rows are written: the pairs the self radius search visits are
+ * linked on the device.
+ *   Inputs.  `radius`, or `radii` (n_points entries by ORIGINAL point index; non-NULL: `radius` is ignored), as
+ * ptk_search_count_within_self takes them; min_neighbors >= 0.  Let row i be row i of ptk_search_radius_self on the same
+ * handle with the same radius or radii (exact, strict <, the handle's metric, the own entry removed).
+ *   Core.  Point i is core iff row i has at least min_neighbors entries.  min_neighbors = 0 makes every point core: plain
+ * connected components.  DBSCAN's min_samples counts the point itself: min_samples = min_neighbors + 1.
+ *   Edges.  Core points i and j are joined whenever j is in row i OR i is in row j: one direction suffices.  (On an
+ * ordinary tree with one radius the rows are symmetric; with per-point radii, or on a tree read from a stream that does
+ * not belong to its points, they are not.)
+ *   Labels (int32, n_points entries by original point index).  A core point's label is the smallest original index among
+ * the core points of its component.  A non-core point's label is the smallest label among the core points in ITS OWN
+ * row, -1 (noise) if that row holds no core point; a non-core point never passes a label on.  Nothing depends on launch
+ * order, lane order or the number of pieces: two calls give identical arrays.  n_clusters (host forms; may be NULL) is
+ * the number of i with labels[i] == i.
+ *   Radius values, as in the self radius searches.  0 gives empty rows: with min_neighbors = 0 every point is its own
+ * cluster (labels[i] = i), with min_neighbors >= 1 everything is -1.  +inf, FLT_MAX / DBL_MAX and subnormal radii are
+ * valid.  A NaN or negative scalar is PTK_ERR_INVALID.  A NaN or negative radii entry is PTK_ERR_INVALID in the
+ * host-buffer forms and the host loop (the message names the first such row); in the _device forms such a row is empty:
+ * the point is its own cluster if min_neighbors = 0, otherwise non-core, and it can still be another point's neighbour.
+ *   Where the device serves it: exactly the handles ptk_search_count_within_self serves, refused through the same check
+ * with the same messages, naming ptk_host_cluster_within_self (every float32 handle, the topological metrics
+ * included).  There is no staged route.  A host-only handle is PTK_ERR_DEVICE, a null labels with n_points > 0
+ * PTK_ERR_INVALID.
+ *   State.  The handle's radius capture is neither read nor invalidated.  The first call with min_neighbors > 0 builds
+ * the handle's count side table if it has none.  The _device forms otherwise only enqueue on `stream`: they allocate
+ * nothing, do not wait, and need no scratch beyond d_labels (the float64 form takes the handle's stack block, which
+ * grows on first use).  In the host form only the radii go up and the labels come down. */
+int ptk_cluster_within_self(const ptk_tree* tree, float radius, const float* radii, uint64_t min_neighbors,
+                            int32_t* labels, uint64_t* n_clusters);
+int ptk_cluster_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, uint64_t min_neighbors,
+                                   int32_t* d_labels, void* stream);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -501,6 +536,10 @@ int ptk_host_search_count_within_self(const ptk_tree* tree, const float* points,
                                       uint64_t max_count, uint64_t* counts);
 int ptk_host_search_radius_self(const ptk_tree* tree, const float* points, float radius, const float* radii, int sort,
                                 uint64_t* offsets, ptk_neighbor** out); /* *out: ptk_free */
+/* (ptk_cluster_within_self as the contract reads: the rows of ptk_host_search_radius_self, a sequential union-find over
+ * them, then the border rule; every metric, the topological ones included) */
+int ptk_host_cluster_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
+                                 uint64_t min_neighbors, int32_t* labels, uint64_t* n_clusters);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 
@@ -614,6 +653,11 @@ int ptk_search64_count_within_self_device(const ptk_tree64* tree, double radius,
                                           uint64_t* d_counts, void* stream);
 int ptk_search64_radius_self(const ptk_tree64* tree, double radius, const double* radii, int sort, uint64_t* offsets,
                              ptk_neighbor64** out);
+/* As ptk_cluster_within_self / _device: radii in double. */
+int ptk_search64_cluster_within_self(const ptk_tree64* tree, double radius, const double* radii, uint64_t min_neighbors,
+                                     int32_t* labels, uint64_t* n_clusters);
+int ptk_search64_cluster_within_self_device(const ptk_tree64* tree, double radius, const double* d_radii,
+                                            uint64_t min_neighbors, int32_t* d_labels, void* stream);
 /* As ptk_search_box. */
 int ptk_search64_box(const ptk_tree64* tree, const double* mins,
                      const double* maxs, uint64_t nb, uint64_t* offsets,

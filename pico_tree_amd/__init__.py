@@ -98,6 +98,8 @@ _SIGNATURES = {
                                       c_void_p]),
     "ptk_search_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
     "ptk_search_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "ptk_cluster_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_cluster_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -129,6 +131,7 @@ _SIGNATURES = {
     "ptk_host_search_knn": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_self": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    "ptk_host_cluster_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -156,6 +159,8 @@ _SIGNATURES = {
     "ptk_search64_knn_device": (c_int, [c_void_p, c_void_p, c_uint64, c_uint32, c_double, c_void_p, c_void_p]),
     "ptk_search64_knn_self": (c_int, [c_void_p, c_uint32, c_void_p]),
     "ptk_search64_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "ptk_search64_cluster_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_cluster_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_count_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p]),
     "ptk_search64_count_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_radius_self": (c_int, [c_void_p, c_double, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -1156,6 +1161,49 @@ class KdTree:
                      lambda lib: lib.ptk_host_search_radius_self(self._h, self._pts.ctypes.data, r, rp, int(bool(sort)),
                                                                  offsets.ctypes.data, byref(rows)))
         return DArray(offsets, _adopt(lib, rows, int(offsets[-1]), self._neighbor))
+
+    def cluster_within_self(self, radius, min_neighbors: int = 0, compact: bool = False, device: bool = False):
+        """``cluster_within_self(radius, min_neighbors=0, compact=False, device=False)`` -- the clusters of the tree's
+        points: the connected components of the fixed-radius graph, with DBSCAN's core-point rule.
+
+        With row i being :meth:`search_radius_self`'s row i: point i is *core* iff that row has at least
+        ``min_neighbors`` entries (0: every point; DBSCAN's ``min_samples`` is ``min_neighbors + 1``); core points i and
+        j are joined whenever j is in row i or i in row j.  A core point's label is the smallest original index among
+        the core points of its component; a non-core point takes the smallest label among the core points of its own
+        row, ``-1`` (noise) without one, and passes nothing on.  ``radius`` is a scalar or an array of ``npts`` radii
+        indexed by original point index.  No rows are written (``ptk_cluster_within_self`` /
+        ``ptk_search64_cluster_within_self``).  Returns an ``int32[npts]`` array; with ``device=True`` an ``int32`` CUDA
+        tensor on the tree's device, enqueued on the current torch stream.  ``compact=True`` renumbers the clusters
+        ``0..C-1`` in ascending order of their representative index; noise stays ``-1``.  Served where
+        :meth:`count_within_self` is; the rest is refused (``allow_host_loop`` serves float32 trees)."""
+        min_neighbors = int(min_neighbors)
+        if min_neighbors < 0:
+            raise ValueError("min_neighbors must be >= 0")
+        r, radii = self._self_radii(radius, device)
+        n = self._npts
+        lib = _load()
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            out = torch.empty((n,), dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            fn = lib.ptk_search64_cluster_within_self_device if self._f64 else lib.ptk_cluster_within_self_device
+            _check(fn(self._h, r, radii.data_ptr() if radii is not None else None, min_neighbors, out.data_ptr(), stream))
+            if compact:
+                _, inverse = torch.unique(out, sorted=True, return_inverse=True)
+                # (the values ascend: a leading -1, if there is noise, takes rank 0)
+                out = (inverse - (out.min() < 0).to(inverse.dtype)).to(torch.int32) if n else out
+            return out
+        labels = np.zeros((n,), dtype=np.int32)
+        rp = radii.ctypes.data if radii is not None else None
+        fn = lib.ptk_search64_cluster_within_self if self._f64 else lib.ptk_cluster_within_self
+        self._served(fn(self._h, r, rp, min_neighbors, labels.ctypes.data, None),
+                     lambda lib: lib.ptk_host_cluster_within_self(self._h, self._pts.ctypes.data, r, rp, min_neighbors,
+                                                                  labels.ctypes.data, None))
+        if compact and n:
+            values, inverse = np.unique(labels, return_inverse=True)
+            labels = (inverse.reshape(-1) - (1 if values[0] < 0 else 0)).astype(np.int32)
+        return labels
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

@@ -2493,6 +2493,78 @@ int ptk_search_radius_self(const ptk_tree* t, float radius, const float* radii, 
       });
 }
 
+// ---- cluster_within_self (ptk.h; the passes: ptk_kernels_cluster.hpp) -------------------------------------
+
+// Enqueues the passes on `stream`, each over all pieces of leaf positions before the next: d_labels is the only working
+// array, nothing is allocated but the handle's count side table on its first use (min_neighbors > 0: the mark pass reads
+// it), nothing is waited for.  The handle's radius capture is neither read nor invalidated.
+int ptk_cluster_within_self_device(const ptk_tree* t, float radius, const float* d_radii, uint64_t min_neighbors,
+                                   int32_t* d_labels, void* stream) {
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_labels, "cluster_within_self",
+                             "ptk_host_cluster_within_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  if (min_neighbors > 0) {
+    rc = count_table_of(t, s);
+    if (rc != PTK_OK) return rc;
+  }
+  const bool shortcut = knob_int("count_shortcut", 1) != 0;
+  const bool compress = knob_int("cluster_compress", ptkf::kClusterCompress ? 1 : 0) != 0;
+  const uint64_t np = t->n_points;
+  auto traversal = [&](int pass) {
+    return in_batch_pieces(np, [&](uint64_t first, uint64_t n) {
+      return ptkf::cluster_self(t, pass, first, n, radius, d_radii, min_neighbors, shortcut, compress, d_labels, s);
+    });
+  };
+  auto elementwise = [&](int pass) {
+    Timer timer(t, s);
+    const int erc = ptkf::cluster_elementwise(pass, np, compress, d_labels, s);
+    timer.stop(2, 0);
+    return erc;
+  };
+  rc = min_neighbors == 0 ? elementwise(ptkf::kClusterInit) : traversal(ptkf::kClusterMark);
+  if (rc == PTK_OK) rc = traversal(ptkf::kClusterLink);
+  if (rc == PTK_OK) rc = elementwise(ptkf::kClusterFlatten);
+  if (rc == PTK_OK && min_neighbors > 0) rc = traversal(ptkf::kClusterBorder);
+  if (rc == PTK_OK && min_neighbors > 0) rc = elementwise(ptkf::kClusterDecode);
+  return rc;
+}
+
+// The host form: only the radii go up, the labels come down; n_clusters (may be null) counts the labels[i] == i.
+int ptk_cluster_within_self(const ptk_tree* t, float radius, const float* radii, uint64_t min_neighbors, int32_t* labels,
+                            uint64_t* n_clusters) {
+  if (n_clusters != nullptr) *n_clusters = 0;
+  const int rc = check_radius_self(t, radius, radii, /*host_values=*/true, labels, "cluster_within_self",
+                                   "ptk_host_cluster_within_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t out_bytes = (size_t)t->n_points * sizeof(int32_t);
+  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
+  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
+  if (src != PTK_OK) return src;
+  const float* d_radii = nullptr;
+  if (radii != nullptr) {
+    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
+    d_radii = reinterpret_cast<const float*>(io.d_in);
+  }
+  src = ptk_cluster_within_self_device(t, radius, d_radii, min_neighbors, reinterpret_cast<int32_t*>(io.d_out), io.search[0]);
+  if (src != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return src;
+  }
+  PTK_HIP(hipMemcpyAsync(labels, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
+  return PTK_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -754,6 +754,13 @@ inline int check_radius_self(const Tree* t, double radius, const Real* radii, bo
   return PTK_OK;
 }
 
+// cluster_within_self (ptk.h): n_clusters of the host forms -- the labels that name their own entry.
+inline uint64_t count_cluster_roots(const int32_t* labels, uint64_t n) {
+  uint64_t roots = 0;
+  for (uint64_t i = 0; i < n; ++i) roots += labels[i] == (int32_t)i ? 1u : 0u;
+  return roots;
+}
+
 inline float inv_ratio(float e) { return 1.0f / e; }
 
 

@@ -1429,6 +1429,71 @@ int ptk_search64_radius_self(const ptk_tree64* t, double radius, const double* r
       });
 }
 
+// cluster_within_self in double (the passes: ptk_kernels_cluster.hpp), each over all pieces of leaf positions before the
+// next; the record stacks of a launch live in the handle's stack block (the lease's piece), d_labels is the only
+// working array.
+int ptk_search64_cluster_within_self_device(const ptk_tree64* t, double radius, const double* d_radii, uint64_t min_neighbors,
+                                            int32_t* d_labels, void* stream) {
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_labels, "cluster_within_self",
+                             "kd_tree::cluster_within_self, one point at a time");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  if (min_neighbors > 0) {
+    rc = count_table64_of(t, s);
+    if (rc != PTK_OK) return rc;
+  }
+  Stack64Lease lease(t, s);
+  rc = lease.acquire(t->n_points);
+  if (rc != PTK_OK) return rc;
+  const bool shortcut = knob_int("count_shortcut", 1) != 0;
+  const bool compress = knob_int("cluster_compress", ptkf::kClusterCompress ? 1 : 0) != 0;
+  const uint64_t np = t->n_points;
+  auto traversal = [&](int pass) {
+    int prc = PTK_OK;
+    for (uint64_t first = 0; first < np && prc == PTK_OK; first += lease.piece)
+      prc = ptkf::cluster64_self(t->dev, t->metric.load(), static_cast<const ptk::CountBox64*>(t->d_count_table), pass, first,
+                                 std::min<uint64_t>(lease.piece, np - first), radius, d_radii, min_neighbors, shortcut, compress,
+                                 d_labels, lease.stack, t->slots, s);
+    return prc;
+  };
+  rc = min_neighbors == 0 ? ptkf::cluster_elementwise(ptkf::kClusterInit, np, compress, d_labels, s)
+                          : traversal(ptkf::kClusterMark);
+  if (rc == PTK_OK) rc = traversal(ptkf::kClusterLink);
+  if (rc == PTK_OK) rc = ptkf::cluster_elementwise(ptkf::kClusterFlatten, np, compress, d_labels, s);
+  if (rc == PTK_OK && min_neighbors > 0) rc = traversal(ptkf::kClusterBorder);
+  if (rc == PTK_OK && min_neighbors > 0) rc = ptkf::cluster_elementwise(ptkf::kClusterDecode, np, compress, d_labels, s);
+  return rc;
+}
+
+int ptk_search64_cluster_within_self(const ptk_tree64* t, double radius, const double* radii, uint64_t min_neighbors,
+                                     int32_t* labels, uint64_t* n_clusters) {
+  if (n_clusters != nullptr) *n_clusters = 0;
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, labels, "cluster_within_self",
+                             "kd_tree::cluster_within_self, one point at a time");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  std::lock_guard<std::mutex> io_lock(t->io_mutex);
+  IoBuffer bin, bout;
+  const uint64_t np = t->n_points;
+  hipError_t he = bout.get(t, 1, np * sizeof(int32_t));
+  const double* d_radii = nullptr;
+  if (he == hipSuccess && radii != nullptr) {
+    he = bin.get(t, 0, np * sizeof(double));
+    if (he == hipSuccess) he = hipMemcpy(bin.p, radii, np * sizeof(double), hipMemcpyHostToDevice);
+    d_radii = reinterpret_cast<const double*>(bin.p);
+  }
+  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (the buffers of cluster_within_self): %s", hipGetErrorString(he));
+  rc = ptk_search64_cluster_within_self_device(t, radius, d_radii, min_neighbors, reinterpret_cast<int32_t*>(bout.p), nullptr);
+  if (rc != PTK_OK) return rc;
+  he = hipMemcpy(labels, bout.p, np * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, np);
+  return PTK_OK;
+}
+
 int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs, uint64_t nb, uint64_t* offsets,
                      int32_t** out) {
   if (out != nullptr) *out = nullptr;

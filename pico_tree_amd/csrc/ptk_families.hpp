@@ -150,6 +150,18 @@ int count64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* t
                  ptk::Rec64* stack, uint32_t slots, hipStream_t s);
 int radius64_self_fill(const ptk::DevTree64& dev, int metric, uint64_t first, uint64_t n, double radius, const double* d_radii,
                        const uint64_t* d_offsets, void* d_out, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
+// cluster_within_self (ptk_kernels_cluster.hpp): one pass over d_labels (n_points int32 entries by
+// original index, the only working array).  The traversal passes take leaf positions [first, first + n) of a handle
+// check_radius_self serves, the elementwise ones all n entries; the caller runs every pass over all pieces before the
+// next one, on one stream.  `compress`: find halves its paths.
+constexpr bool kClusterCompress = true;  // (DESIGN.md §8 has the measurement behind the value; test hook cluster_compress)
+enum ClusterPass { kClusterInit, kClusterMark, kClusterLink, kClusterFlatten, kClusterBorder, kClusterDecode };
+int cluster_self(const ptk_tree* t, int pass, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                 uint64_t min_neighbors, bool shortcut, bool compress, int32_t* d_labels, hipStream_t s);
+int cluster64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, int pass, uint64_t first, uint64_t n,
+                   double radius, const double* d_radii, uint64_t min_neighbors, bool shortcut, bool compress,
+                   int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
+int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, hipStream_t s);
 void warm_self();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.

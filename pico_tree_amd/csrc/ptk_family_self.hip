@@ -2,11 +2,13 @@
 // records (3-D float32 trees, the four non-topological metrics, k + 1 <= 64) and the two small kernels of the staged route
 // (the piece's points as query rows; the rule of the contract on the rows the handle's own search returned), float32 and
 // float64; search_radius_self / count_within_self (ptk_kernels_selfr.hpp, K18): the count and fill kernels over the tree's
-// own records, float32 and float64, each written once over its radius source.
+// own records, float32 and float64, each written once over its radius source; cluster_within_self
+// (ptk_kernels_cluster.hpp, K19): the mark, link and border kernels over the same records and the elementwise passes.
 // One of the translation units of libptk.so (ptk_backend_core.hpp).
 
 #include "ptk_families.hpp"
 #include "ptk_kernels_f64.hpp"
+#include "ptk_kernels_cluster.hpp"
 #include "ptk_kernels_selfr.hpp"
 
 namespace {
@@ -93,6 +95,78 @@ int launch_radius64_self_fill(const ptk::DevTree64& dev, uint64_t first, uint64_
   else
     hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, false>), grid, block, smem, s, dev, first, n, radius, d_radii,
                        d_offsets, d_out, stack, slots);
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
+}
+
+// cluster_within_self: one traversal pass over leaf positions [first, first + n) (ptkf::ClusterPass).  Profile kinds: the
+// mark and border passes count as the search, the link pass as its tail.
+template <int S, int OVF, class M>
+int launch_cluster_self(const ptk_tree* t, int pass, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                        uint64_t min_neighbors, bool shortcut, bool compress, int32_t* d_labels, hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+  const size_t smem = (size_t)S * 64 * 8;
+  const auto* table = static_cast<const ptk::CountBox*>(t->d_count_table);
+  const bool per_row = d_radii != nullptr;
+  Timer timer(t, s);
+#define PTK_CLUSTER_LINK(PER_ROW, COMPRESS)                                                                               \
+  hipLaunchKernelGGL((ptk::cluster_link_kernel<S, OVF, 64, kGenLeafB, PER_ROW, COMPRESS, M>), grid, block, smem, s, t->dev, \
+                     t->dim, first, n, radius, d_radii, d_labels)
+  if (pass == ptkf::kClusterMark) {
+    if (per_row)
+      hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, true, M, ptk::ClusterMarkStore>), grid, block, smem, s,
+                         t->dev, table, t->dim, first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, nullptr);
+    else
+      hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, false, M, ptk::ClusterMarkStore>), grid, block, smem, s,
+                         t->dev, table, t->dim, first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, nullptr);
+  } else if (pass == ptkf::kClusterLink) {
+    if (per_row && compress) PTK_CLUSTER_LINK(true, true);
+    else if (per_row) PTK_CLUSTER_LINK(true, false);
+    else if (compress) PTK_CLUSTER_LINK(false, true);
+    else PTK_CLUSTER_LINK(false, false);
+  } else if (per_row) {
+    hipLaunchKernelGGL((ptk::cluster_border_kernel<S, OVF, 64, kGenLeafB, true, M>), grid, block, smem, s, t->dev, t->dim,
+                       first, n, radius, d_radii, d_labels);
+  } else {
+    hipLaunchKernelGGL((ptk::cluster_border_kernel<S, OVF, 64, kGenLeafB, false, M>), grid, block, smem, s, t->dev, t->dim,
+                       first, n, radius, d_radii, d_labels);
+  }
+#undef PTK_CLUSTER_LINK
+  PTK_HIP(hipGetLastError());
+  timer.stop(pass == ptkf::kClusterLink ? 3 : 0, n);
+  return PTK_OK;
+}
+
+template <class M>
+int launch_cluster64_self(const ptk::DevTree64& dev, const ptk::CountBox64* table, int pass, uint64_t first, uint64_t n,
+                          double radius, const double* d_radii, uint64_t min_neighbors, bool shortcut, bool compress,
+                          int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
+  const size_t smem = ptk::lds64_bytes(0, dev.dim);
+  const bool per_row = d_radii != nullptr;
+#define PTK_CLUSTER64_LINK(PER_ROW, COMPRESS)                                                                          \
+  hipLaunchKernelGGL((ptk::cluster64_link_kernel<M, PER_ROW, COMPRESS>), grid, block, smem, s, dev, first, n, radius, \
+                     d_radii, d_labels, stack, slots)
+  if (pass == ptkf::kClusterMark) {
+    if (per_row)
+      hipLaunchKernelGGL((ptk::count64_self_kernel<M, true, ptk::ClusterMarkStore>), grid, block, smem, s, dev, table, first, n,
+                         radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, stack, slots, nullptr);
+    else
+      hipLaunchKernelGGL((ptk::count64_self_kernel<M, false, ptk::ClusterMarkStore>), grid, block, smem, s, dev, table, first, n,
+                         radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, stack, slots, nullptr);
+  } else if (pass == ptkf::kClusterLink) {
+    if (per_row && compress) PTK_CLUSTER64_LINK(true, true);
+    else if (per_row) PTK_CLUSTER64_LINK(true, false);
+    else if (compress) PTK_CLUSTER64_LINK(false, true);
+    else PTK_CLUSTER64_LINK(false, false);
+  } else if (per_row) {
+    hipLaunchKernelGGL((ptk::cluster64_border_kernel<M, true>), grid, block, smem, s, dev, first, n, radius, d_radii, d_labels,
+                       stack, slots);
+  } else {
+    hipLaunchKernelGGL((ptk::cluster64_border_kernel<M, false>), grid, block, smem, s, dev, first, n, radius, d_radii, d_labels,
+                       stack, slots);
+  }
+#undef PTK_CLUSTER64_LINK
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -185,6 +259,39 @@ int radius64_self_fill(const ptk::DevTree64& dev, int metric, uint64_t first, ui
     default:
       return launch_radius64_self_fill<ptk::Metric64L2>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
   }
+}
+
+int cluster_self(const ptk_tree* t, int pass, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                 uint64_t min_neighbors, bool shortcut, bool compress, int32_t* d_labels, hipStream_t s) {
+  if (t->dim > 3) return fail(PTK_ERR_INVALID, "cluster_self: not a call of the self kernels");
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_cluster_self<16, OVF, M>(t, pass, first, n, radius, d_radii, min_neighbors, shortcut,
+                                                                   compress, d_labels, s))));
+  return rc;
+}
+
+int cluster64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, int pass, uint64_t first, uint64_t n,
+                   double radius, const double* d_radii, uint64_t min_neighbors, bool shortcut, bool compress,
+                   int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
+#define PTK_CLUSTER64(M) \
+  launch_cluster64_self<M>(dev, table, pass, first, n, radius, d_radii, min_neighbors, shortcut, compress, d_labels, stack, slots, s)
+  switch (metric) {
+    case PTK_METRIC_L1: return PTK_CLUSTER64(ptk::Metric64L1);
+    case PTK_METRIC_LPINF: return PTK_CLUSTER64(ptk::Metric64LInf);
+    case PTK_METRIC_LNINF: return PTK_CLUSTER64(ptk::Metric64LNInf);
+    default: return PTK_CLUSTER64(ptk::Metric64L2);
+  }
+#undef PTK_CLUSTER64
+}
+
+int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, hipStream_t s) {
+  const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+  if (pass == kClusterInit) hipLaunchKernelGGL(ptk::cluster_init_kernel, grid, block, 0, s, n, d_labels);
+  else if (pass == kClusterDecode) hipLaunchKernelGGL(ptk::cluster_decode_kernel, grid, block, 0, s, n, d_labels);
+  else if (compress) hipLaunchKernelGGL(ptk::cluster_flatten_kernel<true>, grid, block, 0, s, n, d_labels);
+  else hipLaunchKernelGGL(ptk::cluster_flatten_kernel<false>, grid, block, 0, s, n, d_labels);
+  PTK_HIP(hipGetLastError());
+  return PTK_OK;
 }
 
 // (loads this unit's code object on the calling thread's device: ProcessWarmup of ptk_backend.hip)

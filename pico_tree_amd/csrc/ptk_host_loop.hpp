@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
 #include "pico_tree/internal/visitors.hpp"
 #include "pico_tree/metric.hpp"
@@ -442,6 +443,33 @@ int ptk_host_search_radius_self(const ptk_tree* t, const float* points, float ra
     if (rows == nullptr) return fail(PTK_ERR_NOMEM, "out of host memory");
     for (uint64_t i = 0; i < np; ++i) std::copy(per_row[i].begin(), per_row[i].end(), rows + offsets[i]);
     *out = reinterpret_cast<ptk_neighbor*>(rows);
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// cluster_within_self (ptk.h) as the contract reads: the rows of the self loop above, a sequential union-find over
+// them, then the border rule (pico_tree/internal/cluster.hpp).
+int ptk_host_cluster_within_self(const ptk_tree* t, const float* points, float radius, const float* radii,
+                                 uint64_t min_neighbors, int32_t* labels, uint64_t* n_clusters) {
+  if (n_clusters != nullptr) *n_clusters = 0;
+  const int rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc != PTK_OK) return rc;
+  if (labels == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null labels buffer");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    std::vector<std::vector<neighbor_t>> per_row(t->n_points);
+    radius_self_rows(t, flat, view, points, 0, per_row, [&](uint64_t i) { return radii != nullptr ? radii[i] : radius; });
+    internal::cluster_rows(per_row, min_neighbors, labels);
+    if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
   } catch (const std::exception& ex) {

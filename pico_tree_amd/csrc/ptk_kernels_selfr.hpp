@@ -33,12 +33,19 @@ namespace ptk {
 // A fourth counter of the emulator beside kCountStat*: inside tests refused because the box holds the lane's own point.
 constexpr uint32_t kCountStatOwnBox = 3;
 
+// Where a lane of the count kernels leaves its result: counts[self] = the clamped count.  (The mark pass of
+// cluster_within_self, ptk_kernels_cluster.hpp, puts a core / non-core mark into its labels instead.)
+struct CountSelfStore {
+  using cell = uint64_t;
+  static __device__ __forceinline__ void put(cell* __restrict__ out, uint32_t self, uint64_t count, uint64_t) { out[self] = count; }
+};
+
 // counts[self] = the points other than `self` below the radius, clamped to max_count (0: no limit) after the own point
 // has left.  Leaf positions [first, first + n).  `stats` (the emulator only; null on the device): kCountStat*, kCountStatOwnBox.
-template <int S, int OVF, int BLOCK, int LEAFB, bool PER_ROW, class M = MetricL2>
+template <int S, int OVF, int BLOCK, int LEAFB, bool PER_ROW, class M = MetricL2, class Out = CountSelfStore>
 __global__ __launch_bounds__(BLOCK) void count_self_kernel(
     DevTree t, const CountBox* __restrict__ table, uint32_t dim, uint64_t first, uint64_t n, float radius_all,
-    const float* __restrict__ radii, uint64_t max_count, uint32_t shortcut, uint64_t* __restrict__ counts,
+    const float* __restrict__ radii, uint64_t max_count, uint32_t shortcut, typename Out::cell* __restrict__ counts,
     uint32_t* __restrict__ stats = nullptr) {
   const uint32_t tile = xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral);
   const uint64_t i = (uint64_t)tile * BLOCK + threadIdx.x;
@@ -197,7 +204,7 @@ __global__ __launch_bounds__(BLOCK) void count_self_kernel(
     test = try_box;
     ref = far_is_right ? nd.w : nd.z;
   }
-  counts[self] = count < limit ? count : limit;
+  Out::put(counts, self, count < limit ? count : limit, max_count);
 }
 
 // The fill policy of the self form: RadiusPolicy<kRadiusFill> at e = 1 that appends every accepted point but the lane's own.
@@ -251,10 +258,10 @@ __global__ __launch_bounds__(BLOCK) void radius_self_fill_kernel(
 // are leaf positions [first, first + n), the record stacks those of a launch of n lanes (Stack64: blockIdx.x).  The
 // tiles take the run length of the float32 kernels of this unit (kXcdRunGeneral): consecutive lanes are consecutive
 // leaf positions in both precisions, and one run length per unit keeps xcd_runs the code it was for knn_self_kernel.
-template <class M, bool PER_ROW>
+template <class M, bool PER_ROW, class Out = CountSelfStore>
 __global__ __launch_bounds__(64) void count64_self_kernel(
     DevTree64 t, const CountBox64* __restrict__ table, uint64_t first, uint64_t n, double radius_all,
-    const double* __restrict__ radii, uint64_t max_count, uint32_t shortcut, uint64_t* __restrict__ counts,
+    const double* __restrict__ radii, uint64_t max_count, uint32_t shortcut, typename Out::cell* __restrict__ counts,
     Rec64* __restrict__ stack, uint32_t slots, uint32_t* __restrict__ stats = nullptr) {
   const uint64_t i = (uint64_t)xcd_runs(blockIdx.x, gridDim.x, kXcdRunGeneral) * 64 + threadIdx.x;
   if (i >= n) return;
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(64) void count64_self_kernel(
     }
     if (!entered) break;
   }
-  counts[self] = count < limit ? count : limit;
+  Out::put(counts, self, count < limit ? count : limit, max_count);
 }
 
 // RadiusSelfFillPolicy over double records (the padding word of a record is written as 0).
