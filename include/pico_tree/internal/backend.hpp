@@ -217,6 +217,10 @@ struct ptk_api<float> {
   static int cluster_within_self(tree const* t, float radius, float const* radii, std::uint64_t min_neighbors, std::int32_t* labels) {
     return ptk_cluster_within_self(t, radius, radii, min_neighbors, labels, nullptr);
   }
+  static int normals_within_self(tree const* t, float radius, float const* radii, std::uint64_t min_neighbors,
+                                 float const* viewpoint, ptk_frame* frames, ptk_moments* moments) {
+    return ptk_normals_within_self(t, radius, radii, min_neighbors, viewpoint, frames, moments);
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }

@@ -35,6 +35,7 @@
 #include "internal/cluster.hpp"
 #include "internal/flat_search.hpp"
 #include "internal/flat_tree.hpp"
+#include "internal/local_frame.hpp"
 #include "internal/stream.hpp"
 #include "internal/visitors.hpp"
 #include "metric.hpp"
@@ -436,6 +437,38 @@ class kd_tree {
       std::vector<scalar_type> const& radii, std::int32_t* labels, size_type const min_neighbors = 0) const {
     check_radii(radii, view().size());
     batched_cluster_within_self(scalar_type(0), radii.data(), labels, min_neighbors);
+  }
+
+  //! PCA normals and curvature of the tree's points (float points, three
+  //! dimensions, a non-topological metric).  The neighbourhood of point i is
+  //! row i of search_radius_self (unsorted) plus the point itself; frames[i]
+  //! holds the unit normal (the eigenvector of the smallest eigenvalue of the
+  //! neighbourhood's covariance), the curvature l0 / (l0 + l1 + l2), the
+  //! eigenvalues in ascending order and the row's length.  A row shorter than
+  //! max(min_neighbors, 2) gives NaN.  \p viewpoint (3 scalars, or null) turns
+  //! every normal towards it; without one the component of largest magnitude
+  //! is positive.  \p moments, if given, receives the sums the covariance was
+  //! made from.  Served by the backend (ptk_normals_within_self); where it
+  //! refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined, by the per-point member with the routine of
+  //! internal/local_frame.hpp: the same bytes either way.
+  inline void normals_within_self(
+      scalar_type const radius,
+      std::vector<local_frame>& frames,
+      size_type const min_neighbors = 2,
+      scalar_type const* viewpoint = nullptr,
+      std::vector<local_moments>* moments = nullptr) const {
+    batched_normals_within_self(radius, nullptr, frames, min_neighbors, viewpoint, moments);
+  }
+
+  inline void normals_within_self(
+      std::vector<scalar_type> const& radii,
+      std::vector<local_frame>& frames,
+      size_type const min_neighbors = 2,
+      scalar_type const* viewpoint = nullptr,
+      std::vector<local_moments>* moments = nullptr) const {
+    check_radii(radii, view().size());
+    batched_normals_within_self(scalar_type(0), radii.data(), frames, min_neighbors, viewpoint, moments);
   }
 
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
@@ -877,6 +910,56 @@ class kd_tree {
       internal::ptk_check(
           api::cluster_within_self(device(), radius, radii, static_cast<std::uint64_t>(min_neighbors), labels),
           "ptk_cluster_within_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  void batched_normals_within_self(
+      scalar_type radius,
+      scalar_type const* radii,
+      std::vector<local_frame>& frames,
+      size_type min_neighbors,
+      scalar_type const* viewpoint,
+      std::vector<local_moments>* moments) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(std::is_same_v<scalar_type, float>, "NORMALS_WITHIN_SELF_NEEDS_FLOAT_POINTS");
+    static_assert(!internal::ptk_topological_v<Metric_>, "NORMALS_WITHIN_SELF_NEEDS_A_NON_TOPOLOGICAL_METRIC");
+    auto const points = view();
+    if (points.sdim() != 3) throw std::invalid_argument("pico_tree: normals_within_self needs 3-D points");
+    size_type const n = points.size();
+    frames.resize(n);
+    if (moments != nullptr) moments->resize(n);
+    auto const rows_loop = [&]() {
+      bool const has_view = viewpoint != nullptr;
+      float const vx = has_view ? viewpoint[0] : 0.0f, vy = has_view ? viewpoint[1] : 0.0f, vz = has_view ? viewpoint[2] : 0.0f;
+      internal::host_rows_loop(n, [&](size_type i) {
+        std::vector<neighbor_type> row;
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, row);
+        internal::moment_sums sums;
+        scalar_type const* p = points[static_cast<index_type>(i)];
+        for (neighbor_type const& nb : row) {
+          scalar_type const* o = points[nb.index];
+          sums.add(p[0] - o[0], p[1] - o[1], p[2] - o[2]);
+        }
+        frames[i] = internal::frame_of(sums, static_cast<std::uint64_t>(min_neighbors), has_view, vx, vy, vz, p[0], p[1], p[2]);
+        if (moments != nullptr) (*moments)[i] = sums.record();
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    static_assert(sizeof(local_frame) == sizeof(ptk_frame) && sizeof(local_moments) == sizeof(ptk_moments), "record layout");
+    try {
+      internal::ptk_check(
+          api::normals_within_self(
+              device(), radius, radii, static_cast<std::uint64_t>(min_neighbors), viewpoint,
+              reinterpret_cast<ptk_frame*>(frames.data()),
+              moments != nullptr ? reinterpret_cast<ptk_moments*>(moments->data()) : nullptr),
+          "ptk_normals_within_self");
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

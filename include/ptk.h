@@ -483,6 +483,65 @@ int ptk_cluster_within_self(const ptk_tree* tree, float radius, const float* rad
 int ptk_cluster_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, uint64_t min_neighbors,
                                    int32_t* d_labels, void* stream);
 
+/* ---- normals_within_self: PCA normals and curvature of a tree's own points ------------------------------------------
+ * The moments of each point's neighbourhood, their covariance, and the local frame of it (surface normal, curvature,
+ * eigenvalues), accumulated inside the traversal of the self radius search: no rows are written.  float32 trees with
+ * dim == 3 and the four non-topological metrics.  Contract:
+ *   Inputs.  `radius`, or `radii` (n_points entries by ORIGINAL point index; non-NULL: `radius` is ignored), as
+ * ptk_search_count_within_self takes them; min_neighbors; viewpoint (3 floats on the host, or NULL).
+ *   Row.  Row i is row i of ptk_search_radius_self on the same handle with the same radius or radii and sort = 0: exact,
+ * strict <, the handle's metric, the own entry removed, the reference's traversal order.  Write c for its length and
+ * j_1 .. j_c for its indices in order.
+ *   Offsets.  u_t = p_i - p_{j_t} per component, a float32 subtraction with the query first.  The point itself always
+ * belongs to its neighbourhood with offset 0: it adds nothing to the sums and one to the divisor, m = c + 1, whether or
+ * not its record was in the reference's row.
+ *   Moments.  Every accumulator starts at +0 and takes the offsets in row order: sum[a] = sum[a] + u_a,
+ * outer[ab] = outer[ab] + (u_a * u_b) for ab = xx, xy, xz, yy, yz, zz; every + * - is one IEEE float32 operation, no
+ * contraction, no reassociation.  count = c, pad_ = 0.  Moments are defined bit for bit; a non-finite point gives whatever
+ * this arithmetic gives.
+ *   Covariance.  With M = (float)m: inv = 1 / M, mean_a = sum[a] * inv, C_ab = (outer[ab] * inv) - (mean_a * mean_b).
+ *   Frame.  Computed from C by one routine (include/pico_tree/internal/local_frame.hpp) compiled for the device, the host
+ * loop and the header-only C++ members: cyclic Jacobi with a FIXED 6 sweeps over the pairs (0,1), (0,2), (1,2), a
+ * rotation whose off-diagonal element is exactly 0 skipped, no convergence test; the eigenvalues clamped below at +0 and
+ * sorted ascending by the fixed network (0,1), (1,2), (0,1) with a strict > swap (equal values keep their columns);
+ * normal = the column of eigenvalues[0] divided by its own length; curvature = l0 / ((l0 + l1) + l2), +0 when that sum is
+ * 0.  Only + - * / and sqrtf: the frame is a function of the bits of C.
+ *   Sign.  With a viewpoint v the normal is flipped when ((n_x * w_x) + (n_y * w_y)) + (n_z * w_z) < 0, w = v - p_i;
+ * without one so that its component of largest magnitude is positive (ties: x, then y, then z).
+ *   NaN frames.  normal, curvature and eigenvalues all hold the bits 0x7FC00000 and count = c when
+ * c < max(min_neighbors, 2) -- a plane needs three points -- or when any entry of C is not finite.
+ *   Radius values, as in the self radius searches: 0 gives empty rows (NaN frames, zero moments); +inf, FLT_MAX and
+ * subnormal radii are valid; a NaN or negative scalar is PTK_ERR_INVALID; a NaN or negative radii entry is
+ * PTK_ERR_INVALID in the host-buffer form and the host loop (the message names the row), an empty row in the _device
+ * form.
+ *   Outputs.  frames and moments hold n_points records by original point index; either may be NULL, not both
+ * (PTK_ERR_INVALID with n_points > 0).  Device buffers must be 16-byte aligned (the records are written with 16-byte
+ * stores).
+ *   Refusals.  dim != 3 or a topological metric: PTK_ERR_INVALID from every form, the host loop included (a normal is
+ * defined for Euclidean 3-D points).  A tree of the deep stack class: PTK_ERR_UNSUPPORTED naming
+ * ptk_host_normals_within_self, which serves it.  A host-only handle: PTK_ERR_DEVICE.
+ *   State.  The radius capture is neither read nor invalidated; no side table is needed or built (no shortcut is taken:
+ * the order of the sums is part of the contract).  The _device form only enqueues on `stream`: no allocation, no wait,
+ * no scratch beyond the outputs; `viewpoint` is read at the call.  Two calls give identical bytes.  In the host form only
+ * the radii go up and the records come down. */
+typedef struct ptk_moments {
+  float sum[3];
+  uint32_t count;
+  float outer[6]; /* xx, xy, xz, yy, yz, zz */
+  uint32_t pad_[2];
+} ptk_moments; /* 48 bytes */
+typedef struct ptk_frame {
+  float normal[3];
+  float curvature;
+  float eigenvalues[3]; /* ascending */
+  uint32_t count;
+} ptk_frame; /* 32 bytes */
+int ptk_normals_within_self(const ptk_tree* tree, float radius, const float* radii, uint64_t min_neighbors,
+                            const float* viewpoint, ptk_frame* frames, ptk_moments* moments);
+int ptk_normals_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, uint64_t min_neighbors,
+                                   const float* viewpoint /* host, 3 floats, read at the call */, ptk_frame* d_frames,
+                                   ptk_moments* d_moments, void* stream);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -540,6 +599,11 @@ int ptk_host_search_radius_self(const ptk_tree* tree, const float* points, float
  * them, then the border rule; every metric, the topological ones included) */
 int ptk_host_cluster_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
                                  uint64_t min_neighbors, int32_t* labels, uint64_t* n_clusters);
+/* (ptk_normals_within_self as the contract reads: the rows of ptk_host_search_radius_self, unsorted, then the moments and
+ * the frame of pico_tree/internal/local_frame.hpp; every float32 handle with dim == 3 and a non-topological metric, the
+ * deep stack class included; dim != 3 or a topological metric is PTK_ERR_INVALID) */
+int ptk_host_normals_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
+                                 uint64_t min_neighbors, const float* viewpoint, ptk_frame* frames, ptk_moments* moments);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import datasets  # noqa: F401  (re-export)
 
-__all__ = ["KdTree", "KdForest", "save_kd_tree", "load_kd_tree", "Metric", "NEIGHBOR", "NEIGHBOR64", "DArray", "DeviceNeighbors", "PtkError",
+__all__ = ["KdTree", "KdForest", "save_kd_tree", "load_kd_tree", "Metric", "NEIGHBOR", "NEIGHBOR64", "FRAME", "MOMENTS", "DArray", "DeviceNeighbors", "PtkError",
            "library_path", "device_count", "datasets", "trim_pinned_pool", "registered", "empty_pinned"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +39,9 @@ _LIB_PATH = os.environ.get("PTK_LIBRARY") or os.path.join(_HERE, "csrc", "libptk
 
 #: Result record; identical to the reference binding's neighbor dtype.
 NEIGHBOR = np.dtype([("index", "<i4"), ("distance", "<f4")])
+#: ptk_frame / ptk_moments (ptk.h): the records of KdTree.normals_within_self
+FRAME = np.dtype([("normal", "<f4", (3,)), ("curvature", "<f4"), ("eigenvalues", "<f4", (3,)), ("count", "<u4")])
+MOMENTS = np.dtype([("sum", "<f4", (3,)), ("count", "<u4"), ("outer", "<f4", (6,)), ("pad_", "<u4", (2,))])
 #: The same record of a tree over float64 points: ``neighbor<int, double>`` is 16 bytes with the
 #: distance at offset 8, which is what the reference binding's PYBIND11_NUMPY_DTYPE yields for it
 #: (_pyco_tree/def_core.hpp:17-18).
@@ -100,6 +103,9 @@ _SIGNATURES = {
     "ptk_search_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
     "ptk_cluster_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_cluster_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_normals_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "ptk_normals_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
+                                               c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -132,6 +138,8 @@ _SIGNATURES = {
     "ptk_host_search_knn_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_uint32, c_float, c_void_p]),
     "ptk_host_search_knn_self": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
     "ptk_host_cluster_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_host_normals_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p,
+                                             c_void_p]),
     "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -1204,6 +1212,57 @@ class KdTree:
             values, inverse = np.unique(labels, return_inverse=True)
             labels = (inverse.reshape(-1) - (1 if values[0] < 0 else 0)).astype(np.int32)
         return labels
+
+    def normals_within_self(self, radius, min_neighbors: int = 2, viewpoint=None, moments: bool = False,
+                            device: bool = False):
+        """``normals_within_self(radius, min_neighbors=2, viewpoint=None, moments=False, device=False)`` -- the surface
+        normal, curvature and covariance eigenvalues of every tree point's neighbourhood (PCA normals).
+
+        The neighbourhood of point i is :meth:`search_radius_self`'s row i plus the point itself; its covariance is
+        accumulated inside the traversal, no rows are written (``ptk_normals_within_self``).  Returns a structured
+        array of dtype :data:`FRAME` by original point index: ``normal`` (unit length, the eigenvector of the smallest
+        eigenvalue), ``curvature`` = l0 / (l0 + l1 + l2), ``eigenvalues`` (ascending) and ``count`` (the row's
+        length).  A row shorter than ``max(min_neighbors, 2)`` gives NaN.  ``viewpoint`` (3 numbers) turns every normal
+        towards it; without one the component of largest magnitude is positive.  ``radius`` is a scalar or an array
+        of ``npts`` radii indexed by original point index.  With ``moments=True`` returns ``(frames, moments)``, the
+        second of dtype :data:`MOMENTS`: the sums the covariance was made from.  With ``device=True`` the records are
+        ``uint8`` CUDA tensors ``[npts, 32]`` / ``[npts, 48]`` on the tree's device, enqueued on the current torch
+        stream.  float32 trees with three dimensions and a non-topological metric; served where
+        :meth:`count_within_self` is, the rest is refused (``allow_host_loop`` serves deep trees)."""
+        self._float32_only("normals_within_self")
+        min_neighbors = int(min_neighbors)
+        if min_neighbors < 0:
+            raise ValueError("min_neighbors must be >= 0")
+        view = None
+        if viewpoint is not None:
+            try:
+                view = np.ascontiguousarray(viewpoint, dtype=np.float32)
+            except (TypeError, ValueError) as ex:
+                raise ValueError(f"viewpoint: not an array of numbers ({ex})") from None
+            if view.shape != (3,):
+                raise ValueError("viewpoint must hold 3 numbers")
+        vp = view.ctypes.data if view is not None else None
+        r, radii = self._self_radii(radius, device)
+        n = self._npts
+        lib = _load()
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            frames = torch.empty((n, FRAME.itemsize), dtype=torch.uint8, device=dev)
+            mom = torch.empty((n, MOMENTS.itemsize), dtype=torch.uint8, device=dev) if moments else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.ptk_normals_within_self_device(self._h, r, radii.data_ptr() if radii is not None else None,
+                                                      min_neighbors, vp, frames.data_ptr(),
+                                                      mom.data_ptr() if moments else None, stream))
+            return (frames, mom) if moments else frames
+        frames = np.zeros((n,), dtype=FRAME)
+        mom = np.zeros((n,), dtype=MOMENTS) if moments else None
+        mp = mom.ctypes.data if moments else None
+        rp = radii.ctypes.data if radii is not None else None
+        self._served(lib.ptk_normals_within_self(self._h, r, rp, min_neighbors, vp, frames.ctypes.data, mp),
+                     lambda lib: lib.ptk_host_normals_within_self(self._h, self._pts.ctypes.data, r, rp, min_neighbors, vp,
+                                                                  frames.ctypes.data, mp))
+        return (frames, mom) if moments else frames
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

@@ -2565,6 +2565,58 @@ int ptk_cluster_within_self(const ptk_tree* t, float radius, const float* radii,
   return PTK_OK;
 }
 
+// ---- normals_within_self (ptk.h; the kernel: ptk_kernels_frames.hpp) ----------------------------------------
+
+// Enqueues frames_self_kernel over ranges of leaf positions: no scratch, nothing allocated, nothing waited for, no side
+// table (no shortcut is taken).  The handle's radius capture is neither read nor invalidated.
+int ptk_normals_within_self_device(const ptk_tree* t, float radius, const float* d_radii, uint64_t min_neighbors,
+                                   const float* viewpoint, ptk_frame* d_frames, ptk_moments* d_moments, void* stream) {
+  const int rc = check_normals_self(t, radius, d_radii, /*host_values=*/false, d_frames, d_moments);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  return in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+    return ptkf::frames_self(t, first, n, radius, d_radii, min_neighbors, viewpoint, d_frames, d_moments, s);
+  });
+}
+
+// The host form: only the radii go up, the records come down through the handle's io blocks.
+int ptk_normals_within_self(const ptk_tree* t, float radius, const float* radii, uint64_t min_neighbors,
+                            const float* viewpoint, ptk_frame* frames, ptk_moments* moments) {
+  const int rc = check_normals_self(t, radius, radii, /*host_values=*/true, frames, moments);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const size_t frame_bytes = frames != nullptr ? (size_t)t->n_points * sizeof(ptk_frame) : 0;
+  const size_t moment_bytes = moments != nullptr ? (size_t)t->n_points * sizeof(ptk_moments) : 0;
+  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  int src = grow_device_block(&io.d_out, &io.out_capacity, frame_bytes + moment_bytes);
+  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
+  if (src != PTK_OK) return src;
+  const float* d_radii = nullptr;
+  if (radii != nullptr) {
+    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
+    d_radii = reinterpret_cast<const float*>(io.d_in);
+  }
+  // (the frames first: a run of 32-byte records keeps the moments behind it 16-byte aligned)
+  char* base = reinterpret_cast<char*>(io.d_out);
+  auto* d_frames = frames != nullptr ? reinterpret_cast<ptk_frame*>(base) : nullptr;
+  auto* d_moments = moments != nullptr ? reinterpret_cast<ptk_moments*>(base + frame_bytes) : nullptr;
+  src = ptk_normals_within_self_device(t, radius, d_radii, min_neighbors, viewpoint, d_frames, d_moments, io.search[0]);
+  if (src != PTK_OK) {
+    (void)hipStreamSynchronize(io.search[0]);
+    return src;
+  }
+  if (frames != nullptr) PTK_HIP(hipMemcpyAsync(frames, d_frames, frame_bytes, hipMemcpyDeviceToHost, io.search[0]));
+  if (moments != nullptr) PTK_HIP(hipMemcpyAsync(moments, d_moments, moment_bytes, hipMemcpyDeviceToHost, io.search[0]));
+  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  return PTK_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -754,6 +754,17 @@ inline int check_radius_self(const Tree* t, double radius, const Real* radii, bo
   return PTK_OK;
 }
 
+// normals_within_self (ptk.h): a normal is defined for Euclidean 3-D points -- dim != 3 and the topological metrics are
+// PTK_ERR_INVALID from every form; then the checks of check_radius_self (either output may be null, not both).
+inline int check_normals_self(const ptk_tree* t, double radius, const float* radii, bool host_values, const void* frames,
+                              const void* moments) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  if (t->dim != 3) return fail(PTK_ERR_INVALID, "normals_within_self: a normal is defined for 3-D points, not dim %u", t->dim);
+  if (topological(t)) return fail(PTK_ERR_INVALID, "normals_within_self: a normal is not defined under a topological metric");
+  return check_radius_self(t, radius, radii, host_values, frames != nullptr ? frames : moments, "normals_within_self",
+                           "ptk_host_normals_within_self");
+}
+
 // cluster_within_self (ptk.h): n_clusters of the host forms -- the labels that name their own entry.
 inline uint64_t count_cluster_roots(const int32_t* labels, uint64_t n) {
   uint64_t roots = 0;

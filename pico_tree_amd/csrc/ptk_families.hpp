@@ -162,6 +162,11 @@ int cluster64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64*
                    double radius, const double* d_radii, uint64_t min_neighbors, bool shortcut, bool compress,
                    int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s);
 int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, hipStream_t s);
+// normals_within_self (ptk_kernels_frames.hpp): the frames and / or moments (either may be null) of
+// leaf positions [first, first + n) of a float32 handle with dim == 3 that check_radius_self serves; `view` null: no
+// viewpoint, else 3 host floats.
+int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t min_neighbors,
+                const float* view, ptk_frame* d_frames, ptk_moments* d_moments, hipStream_t s);
 void warm_self();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.

@@ -3,12 +3,14 @@
 // (the piece's points as query rows; the rule of the contract on the rows the handle's own search returned), float32 and
 // float64; search_radius_self / count_within_self (ptk_kernels_selfr.hpp, K18): the count and fill kernels over the tree's
 // own records, float32 and float64, each written once over its radius source; cluster_within_self
-// (ptk_kernels_cluster.hpp, K19): the mark, link and border kernels over the same records and the elementwise passes.
+// (ptk_kernels_cluster.hpp, K19): the mark, link and border kernels over the same records and the elementwise passes;
+// normals_within_self (ptk_kernels_frames.hpp, K20): the moments and frames kernel over the same records.
 // One of the translation units of libptk.so (ptk_backend_core.hpp).
 
 #include "ptk_families.hpp"
 #include "ptk_kernels_f64.hpp"
 #include "ptk_kernels_cluster.hpp"
+#include "ptk_kernels_frames.hpp"
 #include "ptk_kernels_selfr.hpp"
 
 namespace {
@@ -171,6 +173,26 @@ int launch_cluster64_self(const ptk::DevTree64& dev, const ptk::CountBox64* tabl
   return PTK_OK;
 }
 
+// normals_within_self: the launch geometry of the self fill kernel.
+template <int S, int OVF, class M>
+int launch_frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                       uint64_t min_neighbors, const float* view, ptk::lf::frame3* d_frames, ptk::lf::moments3* d_moments,
+                       hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  const uint32_t has_view = view != nullptr ? 1u : 0u;
+  const float vx = view != nullptr ? view[0] : 0.0f, vy = view != nullptr ? view[1] : 0.0f, vz = view != nullptr ? view[2] : 0.0f;
+  Timer timer(t, s);
+  if (d_radii != nullptr)
+    hipLaunchKernelGGL((ptk::frames_self_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                       t->dev, t->dim, first, n, radius, d_radii, min_neighbors, has_view, vx, vy, vz, d_frames, d_moments);
+  else
+    hipLaunchKernelGGL((ptk::frames_self_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
+                       t->dev, t->dim, first, n, radius, d_radii, min_neighbors, has_view, vx, vy, vz, d_frames, d_moments);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, n);
+  return PTK_OK;
+}
+
 static __global__ void warm_self_kernel() {}
 
 }  // namespace
@@ -282,6 +304,17 @@ int cluster64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64*
     default: return PTK_CLUSTER64(ptk::Metric64L2);
   }
 #undef PTK_CLUSTER64
+}
+
+int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t min_neighbors,
+                const float* view, ptk_frame* d_frames, ptk_moments* d_moments, hipStream_t s) {
+  static_assert(sizeof(ptk_frame) == sizeof(ptk::lf::frame3) && sizeof(ptk_moments) == sizeof(ptk::lf::moments3), "record layout");
+  if (t->dim != 3) return fail(PTK_ERR_INVALID, "frames_self: not a call of the frames kernel");
+  auto* f = reinterpret_cast<ptk::lf::frame3*>(d_frames);
+  auto* m = reinterpret_cast<ptk::lf::moments3*>(d_moments);
+  int rc = PTK_OK;
+  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_frames_self<16, OVF, M>(t, first, n, radius, d_radii, min_neighbors, view, f, m, s))));
+  return rc;
 }
 
 int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, hipStream_t s) {

@@ -21,6 +21,7 @@
 
 #include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
+#include "pico_tree/internal/local_frame.hpp"
 #include "pico_tree/internal/visitors.hpp"
 #include "pico_tree/metric.hpp"
 
@@ -226,23 +227,26 @@ int radius_rows(const ptk_tree* t, const float* points, const float* q, uint64_t
   return PTK_OK;
 }
 
+// Row i of the self radius searches: the radius search of point i, the own entry removed.
+inline void radius_self_row(const ptk_tree* t, const flat_t& flat, const view_t& view, const float* points, uint64_t i,
+                            float radius, int sort, std::vector<neighbor_t>& row) {
+  internal::radius_visitor<neighbor_t> v(radius, row);
+  search_one(t, flat, view, points + i * t->dim, v);
+  if (sort) v.sort();
+  for (size_t j = 0; j < row.size(); ++j) {
+    if (row[j].index == (int)i) {
+      row.erase(row.begin() + (std::ptrdiff_t)j);
+      break;
+    }
+  }
+}
+
 // search_radius_self (ptk.h) as the contract reads: the reference's radius search of each of the tree's own points, then
 // the removal of the entry whose index is the row's (an index occurs at most once in a row).  per_row[i]: row i.
 template <class RadiusOf>
 void radius_self_rows(const ptk_tree* t, const flat_t& flat, const view_t& view, const float* points, int sort,
                       std::vector<std::vector<neighbor_t>>& per_row, RadiusOf&& radius_of) {
-  rows_loop(t->n_points, [&](uint64_t i) {
-    std::vector<neighbor_t>& row = per_row[i];
-    internal::radius_visitor<neighbor_t> v(radius_of(i), row);
-    search_one(t, flat, view, points + i * t->dim, v);
-    if (sort) v.sort();
-    for (size_t j = 0; j < row.size(); ++j) {
-      if (row[j].index == (int)i) {
-        row.erase(row.begin() + (std::ptrdiff_t)j);
-        break;
-      }
-    }
-  });
+  rows_loop(t->n_points, [&](uint64_t i) { radius_self_row(t, flat, view, points, i, radius_of(i), sort, per_row[i]); });
 }
 
 // The argument checks of the two self loops: `radii` null -> the scalar radius; else n_points entries, scanned by row.
@@ -470,6 +474,49 @@ int ptk_host_cluster_within_self(const ptk_tree* t, const float* points, float r
     radius_self_rows(t, flat, view, points, 0, per_row, [&](uint64_t i) { return radii != nullptr ? radii[i] : radius; });
     internal::cluster_rows(per_row, min_neighbors, labels);
     if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// normals_within_self (ptk.h) as the contract reads: the row of the self loop above for each point, unsorted, then the
+// moments and the frame of pico_tree/internal/local_frame.hpp.  Every float32 handle with dim == 3 and a
+// non-topological metric, the deep stack class included.
+int ptk_host_normals_within_self(const ptk_tree* t, const float* points, float radius, const float* radii,
+                                 uint64_t min_neighbors, const float* viewpoint, ptk_frame* frames, ptk_moments* moments) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  if (t->dim != 3) return fail(PTK_ERR_INVALID, "normals_within_self: a normal is defined for 3-D points, not dim %u", t->dim);
+  if (topological(t)) return fail(PTK_ERR_INVALID, "normals_within_self: a normal is not defined under a topological metric");
+  const int rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc != PTK_OK) return rc;
+  if (frames == nullptr && moments == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+  static_assert(sizeof(ptk_frame) == sizeof(pico_tree::internal::frame3), "record layout");
+  static_assert(sizeof(ptk_moments) == sizeof(pico_tree::internal::moments3), "record layout");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    const bool has_view = viewpoint != nullptr;
+    const float vx = has_view ? viewpoint[0] : 0.0f, vy = has_view ? viewpoint[1] : 0.0f, vz = has_view ? viewpoint[2] : 0.0f;
+    rows_loop(t->n_points, [&](uint64_t i) {
+      std::vector<neighbor_t> row;
+      radius_self_row(t, flat, view, points, i, radii != nullptr ? radii[i] : radius, 0, row);
+      const internal::moment_sums sums = internal::sums_of_row(points, i, row);
+      if (frames != nullptr) {
+        const internal::frame3 f = internal::frame_of(sums, min_neighbors, has_view, vx, vy, vz, points[3 * i],
+                                                      points[3 * i + 1], points[3 * i + 2]);
+        std::memcpy(frames + i, &f, sizeof f);
+      }
+      if (moments != nullptr) {
+        const internal::moments3 m = sums.record();
+        std::memcpy(moments + i, &m, sizeof m);
+      }
+    });
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
   } catch (const std::exception& ex) {

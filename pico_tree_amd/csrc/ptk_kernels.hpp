@@ -621,6 +621,13 @@ struct takes_leaf_hooks : std::false_type {};
 template <class P>
 struct takes_leaf_hooks<P, std::void_t<decltype(P::kLeafHooks)>> : std::integral_constant<bool, P::kLeafHooks> {};
 
+// Policies that want a point's offset from the query beside its distance (visit_at(idx, d, dx, dy, dz) in place of
+// visit(idx, d) in the plain leaf scan: the differences are in registers there) say so with kOffsetVisit.
+template <class P, class = void>
+struct takes_offsets : std::false_type {};
+template <class P>
+struct takes_offsets<P, std::void_t<decltype(P::kOffsetVisit)>> : std::integral_constant<bool, P::kOffsetVisit> {};
+
 template <int MODE>
 struct RadiusPolicy {  // search_visitor.hpp:127-156 / :252-288
   static constexpr bool kRoundVisit = MODE == kRadiusCapture;
@@ -922,7 +929,11 @@ __device__ __forceinline__ bool traverse(
             PTK_SCALAR(dx);
             PTK_SCALAR(dy);
             PTK_SCALAR(dz);
-            pol.visit(__float_as_int(p[u].w), point_distance3<M>(dx, dy, dz));
+            if constexpr (takes_offsets<Policy>::value) {
+              pol.visit_at(__float_as_int(p[u].w), point_distance3<M>(dx, dy, dz), dx, dy, dz);
+            } else {
+              pol.visit(__float_as_int(p[u].w), point_distance3<M>(dx, dy, dz));
+            }
           }
         }
       }
