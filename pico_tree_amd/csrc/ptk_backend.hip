@@ -1007,14 +1007,11 @@ int launch_knn1_two_phase(const ptk_tree* t, const float* d_q, const uint32_t* p
 template <class M>
 int dispatch_knn1_of(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float e,
                      ptk::Neighbor* d_out, hipStream_t s, Scratch& scratch) {
-  int rc = PTK_OK;
-  switch (ovf_class_of(knn1_depth(t), 16)) {  // (the depth of what is traversed: the view without the piles if there is one)
-    case 0: rc = launch_knn1_two_phase<ptk::kOvfSlots[0], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
-    case 1: rc = launch_knn1_two_phase<ptk::kOvfSlots[1], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
-    case 2: rc = launch_knn1_two_phase<ptk::kOvfSlots[2], M>(t, d_q, perm, nq, e, d_out, s, scratch); break;
-    default: rc = fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", knn1_depth(t));
-  }
-  return rc;
+  // (the depth of what is traversed: the view without the piles if there is one)
+  return ptkd::with_ovf<ptk::kOvfSlots[0], ptk::kOvfSlots[1], ptk::kOvfSlots[2]>(
+      ovf_class_of(knn1_depth(t), 16),
+      [&](auto ovf) { return launch_knn1_two_phase<ovf, M>(t, d_q, perm, nq, e, d_out, s, scratch); },
+      [&] { return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", knn1_depth(t)); });
 }
 // The two-phase k = 1 search: metric_l2_squared, and (r06) metric_l1 on trees without piles (see knn1_two_phase()).
 int dispatch_knn1(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float e,
@@ -1500,7 +1497,7 @@ static int knn_piece_device(const ptk_tree* t, const float* d_q, uint64_t nq, ui
   if (rc != PTK_OK) return rc;
   if (t->dim > 3) return ptkf::knn_nd(t, d_q, perm, nq, k, e, d_out, s, short_tree);
   if (two_phase) return dispatch_knn1(t, d_q, perm, nq, e, d_out, s, scratch);
-  if (k <= knn_reg_max(l2) && !short_tree) return ptkf::knn_reg(t, d_q, perm, nq, k, e, d_out, s, &scratch);
+  if (k <= knn_reg_max() && !short_tree) return ptkf::knn_reg(t, d_q, perm, nq, k, e, d_out, s, &scratch);
   return ptkf::knn_rows(t, d_q, perm, nq, k, e, d_out, s);
 }
 
@@ -2701,8 +2698,7 @@ int box_pass_device(const ptk_tree* t, const float* d_mn, const float* d_mx, uin
     });
   }
   Timer timer(t, s);
-  PTK_WITH_OVF(16, (t->dim > 3 ? launch(std::integral_constant<int, OVF>{}, t->dev_nd, 0, nb)
-                               : launch(std::integral_constant<int, OVF>{}, t->dev, 0, nb)));
+  rc = with_ovf(t, 16, [&](auto ovf) { return t->dim > 3 ? launch(ovf, t->dev_nd, 0, nb) : launch(ovf, t->dev, 0, nb); });
   if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
   timer.stop(kind, queries);

@@ -37,6 +37,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "ptk.h"
+#include "ptk_dispatch.hpp"
 #include "ptk_hostio.hpp"
 #include "ptk_encode.hpp"
 #include "ptk_kernels.hpp"
@@ -877,36 +878,21 @@ inline size_t radius_coop_scratch_bytes(const ptk_tree* t, uint64_t nq) {
 
 // The largest k whose list lives in registers (3-D kernels, every metric): 64 slots (a list of 40 in LDS took 74 ms on
 // BASELINE config 3 where 32 in registers take 7: insert_sorted through LDS is a loop per lane).
-inline uint32_t knn_reg_max(bool) { return 64u; }
+inline uint32_t knn_reg_max() { return 64u; }
 // k <= 64: the k-list in registers (K = 4 / 8 / 16 / 32 / 64 slots compiled).
 
-// Runs CALL with OVF bound to the spill capacity the tree's depth needs.
-#define PTK_WITH_OVF(SLDS, CALL)                                                                            \
-  switch (ovf_class(t, SLDS)) {                                                                             \
-    case 0: { constexpr int OVF = ptk::kOvfSlots[0]; rc = CALL; } break;                                    \
-    case 1: { constexpr int OVF = ptk::kOvfSlots[1]; rc = CALL; } break;                                    \
-    case 2: { constexpr int OVF = ptk::kOvfSlots[2]; rc = CALL; } break;                                    \
-    default: rc = fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth); \
-  }
-
-// Runs CALL with M bound to the metric of the handle (other than L2 squared).
-#define PTK_WITH_METRIC(CALL)                                              \
-  switch (t->metric.load()) {                                             \
-    case PTK_METRIC_L1: { using M = ptk::MetricL1; CALL; } break;         \
-    case PTK_METRIC_LPINF: { using M = ptk::MetricLInf; CALL; } break;    \
-    case PTK_METRIC_LNINF: { using M = ptk::MetricLNInf; CALL; } break;   \
-    default: { using M = ptk::MetricL2; CALL; } break;                    \
-  }
-
-// ---- topological metrics (ptk_kernels_topo.hpp) ------------------------------------------------
-#define PTK_WITH_TOPO(CALL)                                         \
-  if (t->metric.load() == PTK_METRIC_SO2) {                         \
-    using T = ptk::TopoSO2;                                         \
-    CALL;                                                           \
-  } else {                                                          \
-    using T = ptk::TopoSE2;                                         \
-    CALL;                                                           \
-  }
-
+// ---- the tags of a handle (ptk_dispatch.hpp) ---------------------------------------------------
+// f(int_tag<OVF>): the spill capacity the tree's depth needs beside an LDS ring of `s_lds` records.
+template <class F>
+int with_ovf(const ptk_tree* t, int s_lds, F&& f) {
+  return ptkd::with_ovf<ptk::kOvfSlots[0], ptk::kOvfSlots[1], ptk::kOvfSlots[2]>(ovf_class(t, s_lds), std::forward<F>(f), [&] {
+    return fail(PTK_ERR_UNSUPPORTED, "tree depth %u is too deep for the device stack", t->max_depth);
+  });
+}
+// f(type_tag<M>, int_tag<OVF>): the handle's metric (the four Euclidean ones) and its spill capacity.
+template <class F>
+int with_metric_ovf(const ptk_tree* t, int s_lds, F&& f) {
+  return ptkd::with_metric(t->metric.load(), [&](auto m) { return with_ovf(t, s_lds, [&](auto ovf) { return f(m, ovf); }); });
+}
 
 }  // namespace ptkb

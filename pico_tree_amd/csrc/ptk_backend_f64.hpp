@@ -364,64 +364,33 @@ int order_batch64(const ptk_tree64* t, const double* d_q, uint64_t nq, hipStream
   return make_permutation64(t, d_q, nq, s, lease, perm, long_first);
 }
 
-#define PTK_WITH_METRIC64(CALL)                         \
-  do {                                                  \
-    const int metric_ = t->metric.load();               \
-    if (metric_ == PTK_METRIC_L1) {                     \
-      using M = ptk::Metric64L1;                        \
-      CALL;                                             \
-    } else if (metric_ == PTK_METRIC_LPINF) {           \
-      using M = ptk::Metric64LInf;                      \
-      CALL;                                             \
-    } else if (metric_ == PTK_METRIC_LNINF) {           \
-      using M = ptk::Metric64LNInf;                     \
-      CALL;                                             \
-    } else if (metric_ == PTK_METRIC_SO2) {             \
-      using M = ptk::Topo64SO2;                         \
-      CALL;                                             \
-    } else if (metric_ == PTK_METRIC_SE2_SQUARED) {     \
-      using M = ptk::Topo64SE2;                         \
-      CALL;                                             \
-    } else {                                            \
-      using M = ptk::Metric64L2;                        \
-      CALL;                                             \
-    }                                                   \
-  } while (0)
-
 template <class M>
 int launch_knn64(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, double e,
                  ptk::Neighbor64* d_out, hipStream_t s, Stack64Lease& lease, bool short_tree = false) {
   const bool d3 = t->dim <= 3;  // q / off in registers: the LDS holds the record ring only
   const size_t smem = ptk::lds64_bytes(d3 ? 0 : 2, t->dim);
   if (smem > 160 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dim %u needs %zu bytes of LDS per wavefront (> 160 KiB)", t->dim, smem);
-  int rc = PTK_OK;
   // k-list in registers for 1 < k <= 64 (it assumes every slot gets filled: not for k > n_points).
-  const int reg = (k > 1 && k <= 64 && !short_tree) ? (k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : 64)))) : 0;
-#define PTK_LAUNCH64(KERNEL)                                                                                          \
-  do {                                                                                                                \
-    rc = allow_lds(KERNEL, smem);                                                                                     \
-    if (rc != PTK_OK) return rc;                                                                                      \
-    for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {                                                               \
-      const uint64_t n = std::min(lease.piece, nq - q0);                                                              \
-      hipLaunchKernelGGL(KERNEL, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k,   \
-                         1.0 / e, d_out, lease.stack, t->slots);                                                     \
-    }                                                                                                                 \
-  } while (0)
-  if (d3) {
-    if (reg == 4) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 4, true>));
-    else if (reg == 8) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 8, true>));
-    else if (reg == 16) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 16, true>));
-    else if (reg == 32) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 32, true>));
-    else if (reg == 64) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 64, true>));
-    else PTK_LAUNCH64((ptk::knn64_kernel<M, true>));
-  } else if constexpr (!M::kTopo) {  // (the topological metrics: dim 1 or 3)
-    if (reg == 4) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 4, false>));
-    else if (reg == 8) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 8, false>));
-    else if (reg == 16) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 16, false>));
-    else if (reg == 32) PTK_LAUNCH64((ptk::knn64_reg_kernel<M, 32, false>));
-    else PTK_LAUNCH64((ptk::knn64_kernel<M, false>));  // (64 slots: dim <= 3 only -- 252 VGPRs with q / off in registers)
-  }
-#undef PTK_LAUNCH64
+  const bool reg = k > 1 && k <= 64 && !short_tree;
+  auto launch = [&](auto kernel) {
+    const int rc = allow_lds(kernel, smem);
+    for (uint64_t q0 = 0; rc == PTK_OK && q0 < nq; q0 += lease.piece) {
+      const uint64_t n = std::min(lease.piece, nq - q0);
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k, 1.0 / e,
+                         d_out, lease.stack, t->slots);
+    }
+    return rc;
+  };
+  const int rc = ptkd::with_bool(d3, [&](auto D3) -> int {
+    if constexpr (!D3 && M::kTopo) return PTK_OK;  // (the topological metrics: dim 1 or 3 -- no kernel, no launch)
+    else if (!reg) return launch(ptk::knn64_kernel<M, D3>);
+    else return ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {
+      // (64 slots: dim <= 3 only -- 252 VGPRs with q / off in registers; k = 33 .. 64 of dim > 3 is the row kernel's)
+      if constexpr (K == 64 && !D3) return launch(ptk::knn64_kernel<M, D3>);
+      else return launch(ptk::knn64_reg_kernel<M, K, D3>);
+    });
+  });
+  if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -438,47 +407,30 @@ int launch_knn64_within(const ptk_tree64* t, const double* d_q, const uint32_t* 
   const bool d3 = t->dim <= 3;
   const size_t smem = ptk::lds64_bytes(d3 ? 0 : 2, t->dim);
   if (smem > 160 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dim %u needs %zu bytes of LDS per wavefront (> 160 KiB)", t->dim, smem);
-  int rc = PTK_OK;
-  // (register list for k <= 64 with dim <= 3, k <= 32 otherwise -- the VGPR budget of launch_knn64)
-  const int reg = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 && d3 ? 64 : 0))));
-#define PTK_LAUNCH64_ONE(KERNEL, A, B)                                                                                \
-  do {                                                                                                                \
-    rc = allow_lds(KERNEL, smem);                                                                                     \
-    if (rc != PTK_OK) return rc;                                                                                      \
-    for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {                                                               \
-      const uint64_t n = std::min(lease.piece, nq - q0);                                                              \
-      hipLaunchKernelGGL(KERNEL, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k,   \
-                         d_out, lease.stack, t->slots, A, B);                                                        \
-    }                                                                                                                 \
-  } while (0)
-  // (NAME<ARGS>: the scalar call's kernel; NAME##_radii... is spelled out by the two macros below)
-#define PTK_LAUNCH64_REG_WITHIN(KK, D3)                                                                               \
-  do {                                                                                                                \
-    if constexpr (kRows) PTK_LAUNCH64_ONE((ptk::knn64_reg_within_radii_kernel<M, KK, D3>), r.radii, r.unseeded);      \
-    else PTK_LAUNCH64_ONE((ptk::knn64_reg_within_kernel<M, KK, D3>), r.seed, r.radius);                               \
-  } while (0)
-#define PTK_LAUNCH64_ROW_WITHIN(D3)                                                                                   \
-  do {                                                                                                                \
-    if constexpr (kRows) PTK_LAUNCH64_ONE((ptk::knn64_within_radii_kernel<M, D3>), r.radii, r.unseeded);              \
-    else PTK_LAUNCH64_ONE((ptk::knn64_within_kernel<M, D3>), r.seed, r.radius);                                       \
-  } while (0)
-  if (d3) {
-    if (reg == 4) PTK_LAUNCH64_REG_WITHIN(4, true);
-    else if (reg == 8) PTK_LAUNCH64_REG_WITHIN(8, true);
-    else if (reg == 16) PTK_LAUNCH64_REG_WITHIN(16, true);
-    else if (reg == 32) PTK_LAUNCH64_REG_WITHIN(32, true);
-    else if (reg == 64) PTK_LAUNCH64_REG_WITHIN(64, true);
-    else PTK_LAUNCH64_ROW_WITHIN(true);
-  } else {
-    if (reg == 4) PTK_LAUNCH64_REG_WITHIN(4, false);
-    else if (reg == 8) PTK_LAUNCH64_REG_WITHIN(8, false);
-    else if (reg == 16) PTK_LAUNCH64_REG_WITHIN(16, false);
-    else if (reg == 32) PTK_LAUNCH64_REG_WITHIN(32, false);
-    else PTK_LAUNCH64_ROW_WITHIN(false);
-  }
-#undef PTK_LAUNCH64_ROW_WITHIN
-#undef PTK_LAUNCH64_REG_WITHIN
-#undef PTK_LAUNCH64_ONE
+  // (`a`, `b`: the two arguments a bounded kernel ends with -- the scalar call's or the per-row call's)
+  auto launch = [&](auto kernel, auto a, auto b) {
+    const int rc = allow_lds(kernel, smem);
+    for (uint64_t q0 = 0; rc == PTK_OK && q0 < nq; q0 += lease.piece) {
+      const uint64_t n = std::min(lease.piece, nq - q0);
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q, perm, q0, n, k, d_out,
+                         lease.stack, t->slots, a, b);
+    }
+    return rc;
+  };
+  const int rc = ptkd::with_bool(d3, [&](auto D3) {
+    auto rows = [&] {
+      if constexpr (kRows) return launch(ptk::knn64_within_radii_kernel<M, D3>, r.radii, r.unseeded);
+      else return launch(ptk::knn64_within_kernel<M, D3>, r.seed, r.radius);
+    };
+    if (k > 64) return rows();
+    return ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {
+      // (register list for k <= 64 with dim <= 3, k <= 32 otherwise -- the VGPR budget of launch_knn64)
+      if constexpr (K == 64 && !D3) return rows();
+      else if constexpr (kRows) return launch(ptk::knn64_reg_within_radii_kernel<M, K, D3>, r.radii, r.unseeded);
+      else return launch(ptk::knn64_reg_within_kernel<M, K, D3>, r.seed, r.radius);
+    });
+  });
+  if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
   return PTK_OK;
   }
@@ -572,24 +524,18 @@ int launch_knn64_capped(const ptk_tree64* t, const double* d_q, const uint32_t* 
   const size_t smem = ptk::lds64_bytes(0, t->dim);
   const size_t coop_smem = ptk::knn64_coop_lds_bytes(kKnn64CoopPool);
   const uint32_t redo_blocks = (uint32_t)std::min<uint64_t>((uint64_t)t->cus, std::max<uint64_t>(1, lease.piece / 64));
-#define PTK_LAUNCH64C(KK)                                                                                             \
-  do {                                                                                                                \
-    for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {                                                               \
-      const uint64_t n = std::min(lease.piece, nq - q0);                                                              \
-      hipLaunchKernelGGL((ptk::knn64_capped_kernel<M, KK>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, \
-                         d_q, perm, q0, n, k, d_out, lease.stack, t->slots, cap, d_ho);                               \
-    }                                                                                                                 \
-    hipLaunchKernelGGL((ptk::knn64_coop_kernel<KK, kKnn64CoopPool, M>), dim3(coop_blocks), dim3(64), coop_smem, s,     \
-                       t->dev, d_q, k, d_out, ho, redo_list, ptk::kMetaRedo, spill, spill_cap);                       \
-    hipLaunchKernelGGL((ptk::knn64_redo_kernel<M, KK>), dim3(redo_blocks), dim3(64), smem, s, t->dev, d_q, k, d_out,   \
-                       meta, ptk::kMetaRedo, redo_list, lease.stack, t->slots);                                       \
-  } while (0)
-  if (k == 1) PTK_LAUNCH64C(1);
-  else if (k <= 4) PTK_LAUNCH64C(4);
-  else if (k <= 8) PTK_LAUNCH64C(8);
-  else if (k <= 16) PTK_LAUNCH64C(16);
-  else PTK_LAUNCH64C(32);
-#undef PTK_LAUNCH64C
+  ptkd::with_slots<1, 4, 8, 16, 32>(k, [&](auto K) {
+    for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {
+      const uint64_t n = std::min(lease.piece, nq - q0);
+      hipLaunchKernelGGL((ptk::knn64_capped_kernel<M, K>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev, d_q,
+                         perm, q0, n, k, d_out, lease.stack, t->slots, cap, d_ho);
+    }
+    hipLaunchKernelGGL((ptk::knn64_coop_kernel<K, kKnn64CoopPool, M>), dim3(coop_blocks), dim3(64), coop_smem, s, t->dev,
+                       d_q, k, d_out, ho, redo_list, ptk::kMetaRedo, spill, spill_cap);
+    hipLaunchKernelGGL((ptk::knn64_redo_kernel<M, K>), dim3(redo_blocks), dim3(64), smem, s, t->dev, d_q, k, d_out, meta,
+                       ptk::kMetaRedo, redo_list, lease.stack, t->slots);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -700,23 +646,6 @@ int launch_radius64_capped(const ptk_tree64* t, const double* d_q, const uint32_
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
-#define PTK_WITH_EUCLID64(CALL)                      \
-  do {                                               \
-    const int metric_ = t->metric.load();            \
-    if (metric_ == PTK_METRIC_L1) {                  \
-      using M = ptk::Metric64L1;                     \
-      CALL;                                          \
-    } else if (metric_ == PTK_METRIC_LPINF) {        \
-      using M = ptk::Metric64LInf;                   \
-      CALL;                                          \
-    } else if (metric_ == PTK_METRIC_LNINF) {        \
-      using M = ptk::Metric64LNInf;                  \
-      CALL;                                          \
-    } else {                                         \
-      using M = ptk::Metric64L2;                     \
-      CALL;                                          \
-    }                                                \
-  } while (0)
 
 template <class M, bool FILL>
 int launch_radius64(const ptk_tree64* t, const double* d_q, const uint32_t* perm, uint64_t nq, double radius, double e,
@@ -727,16 +656,16 @@ int launch_radius64(const ptk_tree64* t, const double* d_q, const uint32_t* perm
   if (smem > 160 * 1024) return fail(PTK_ERR_UNSUPPORTED, "dim %u needs %zu bytes of LDS per wavefront (> 160 KiB)", t->dim, smem);
   int rc = allow_lds(ptk::radius64_kernel<M, FILL, M::kTopo>, smem);
   if (rc != PTK_OK) return rc;
-  for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {
-    const uint64_t n = std::min(lease.piece, nq - q0);
-    if (d3) {
-      hipLaunchKernelGGL((ptk::radius64_kernel<M, FILL, true>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
-                         d_q, perm, q0, n, radius, 1.0 / e, d_counts, d_offsets, d_out, lease.stack, t->slots);
-    } else if constexpr (!M::kTopo) {
-      hipLaunchKernelGGL((ptk::radius64_kernel<M, FILL, false>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
-                         d_q, perm, q0, n, radius, 1.0 / e, d_counts, d_offsets, d_out, lease.stack, t->slots);
+  ptkd::with_bool(d3, [&](auto D3) {
+    if constexpr (D3 || !M::kTopo) {  // (the topological metrics: dim 1 or 3)
+      for (uint64_t q0 = 0; q0 < nq; q0 += lease.piece) {
+        const uint64_t n = std::min(lease.piece, nq - q0);
+        hipLaunchKernelGGL((ptk::radius64_kernel<M, FILL, D3>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
+                           d_q, perm, q0, n, radius, 1.0 / e, d_counts, d_offsets, d_out, lease.stack, t->slots);
+      }
     }
-  }
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -769,20 +698,17 @@ int launch_box64(const ptk_tree64* t, const double* d_mins, const double* d_maxs
   const bool topo = metric == PTK_METRIC_SO2 || metric == PTK_METRIC_SE2_SQUARED;
   const uint32_t s1_mask = !topo ? 0u : (metric == PTK_METRIC_SO2 ? 1u : 4u);
   if (topo && t->dev.outer == nullptr) return fail(PTK_ERR_INVALID, "this topological tree has no outer bounds on the device");
-  int rc = topo ? allow_lds(ptk::box64_kernel<FILL, true>, smem) : allow_lds(ptk::box64_kernel<FILL, false>, smem);
-  if (rc != PTK_OK) return rc;
-  for (uint64_t b0 = 0; b0 < nb; b0 += lease.piece) {
-    const uint64_t n = std::min(lease.piece, nb - b0);
-    if (topo) {
-      hipLaunchKernelGGL((ptk::box64_kernel<FILL, true>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
+  const int rc = ptkd::with_bool(topo, [&](auto TOPO) {
+    const int lds_rc = allow_lds(ptk::box64_kernel<FILL, TOPO>, smem);
+    for (uint64_t b0 = 0; lds_rc == PTK_OK && b0 < nb; b0 += lease.piece) {
+      const uint64_t n = std::min(lease.piece, nb - b0);
+      hipLaunchKernelGGL((ptk::box64_kernel<FILL, TOPO>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
                          static_cast<const double*>(t->d_root), d_mins, d_maxs, b0, n, d_counts, d_offsets, d_out,
                          lease.stack, t->slots, s1_mask);
-    } else {
-      hipLaunchKernelGGL((ptk::box64_kernel<FILL, false>), dim3((uint32_t)((n + 63) / 64)), dim3(64), smem, s, t->dev,
-                         static_cast<const double*>(t->d_root), d_mins, d_maxs, b0, n, d_counts, d_offsets, d_out,
-                         lease.stack, t->slots, 0u);
     }
-  }
+    return lds_rc;
+  });
+  if (rc != PTK_OK) return rc;
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -1007,9 +933,10 @@ int ptk_search64_knn_device(const ptk_tree64* t, const double* d_q, uint64_t nq,
     return launch_knn64_capped<ptk::Metric64L2>(t, d_q, perm, nq, k, cap, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
                                                lease.own);
   }
-  PTK_WITH_METRIC64(rc = launch_knn64<M>(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease,
-                                         short_tree));
-  return rc;
+  return ptkd::with_metric64(t->metric.load(), [&](auto m) {
+    return launch_knn64<ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, e, reinterpret_cast<ptk::Neighbor64*>(d_out), s,
+                                               lease, short_tree);
+  });
 }
 
 // search_knn_self (ptk.h): every float64 tree takes the staged route -- the tree's points, piece by piece
@@ -1068,8 +995,10 @@ int ptk_search64_knn_within_device(const ptk_tree64* t, const double* d_q, uint6
   rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
   if (rc != PTK_OK) return rc;
   const ptkf::WithinOne<double> r{seed, radius};
-  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, r, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease));
-  return rc;
+  return ptkd::with_metric64(t->metric.load(), [&](auto m) {
+    return launch_knn64_within<ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, r,
+                                                      reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease);
+  });
 }
 
 int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, double radius,
@@ -1099,8 +1028,10 @@ int ptk_search64_knn_within_radii_device(const ptk_tree64* t, const double* d_q,
   rc = order_batch64(t, d_q, nq, s, lease, 0, &perm, /*long_first=*/true);
   if (rc != PTK_OK) return rc;
   const ptkf::WithinRows<double> r{d_radii, unseeded ? 1u : 0u};
-  PTK_WITH_METRIC64(rc = launch_knn64_within<M>(t, d_q, perm, nq, k, r, reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease));
-  return rc;
+  return ptkd::with_metric64(t->metric.load(), [&](auto m) {
+    return launch_knn64_within<ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, r,
+                                                      reinterpret_cast<ptk::Neighbor64*>(d_out), s, lease);
+  });
 }
 
 int ptk_search64_knn_within_radii(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t k, const double* radii,
@@ -1157,7 +1088,10 @@ int ptk_search64_count_within_device(const ptk_tree64* t, const double* d_q, uin
                                 t->slots, s);
     return rc;
   }
-  PTK_WITH_METRIC64(rc = (launch_radius64<M, false>(t, d_q, perm, nq, radius, 1.0, d_counts, nullptr, nullptr, s, lease)));
+  rc = ptkd::with_metric64(t->metric.load(), [&](auto m) {
+    return launch_radius64<ptkd::type_of<decltype(m)>, false>(t, d_q, perm, nq, radius, 1.0, d_counts, nullptr, nullptr, s,
+                                                  lease);
+  });
   if (rc != PTK_OK) return rc;
   return ptkf::clamp_counts(d_counts, nq, max_count, s);
 }
@@ -1277,11 +1211,15 @@ int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, doubl
         if (rc == PTK_OK && cap != 0u) {
           rs = radius64_carve(t, nq, lease.own);
           t->last_meta = rs.meta;
-          PTK_WITH_EUCLID64(rc = (launch_radius64_capped<M, false>(t, d_q, perm, nq, radius, e, cap, d_counts, nullptr, nullptr,
-                                                                  nullptr, lease, rs)));
+          rc = ptkd::with_euclid64(t->metric.load(), [&](auto m) {
+            return launch_radius64_capped<ptkd::type_of<decltype(m)>, false>(t, d_q, perm, nq, radius, e, cap, d_counts,
+                nullptr, nullptr, nullptr, lease, rs);
+          });
         } else if (rc == PTK_OK) {
-          PTK_WITH_METRIC64(
-              rc = (launch_radius64<M, false>(t, d_q, perm, nq, radius, e, d_counts, nullptr, nullptr, nullptr, lease)));
+          rc = ptkd::with_metric64(t->metric.load(), [&](auto m) {
+            return launch_radius64<ptkd::type_of<decltype(m)>, false>(t, d_q, perm, nq, radius, e, d_counts, nullptr,
+                                                          nullptr, nullptr, lease);
+          });
         }
         return rc;
       },
@@ -1289,10 +1227,15 @@ int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, doubl
         ptk::Neighbor64* d_out = reinterpret_cast<ptk::Neighbor64*>(d_rows);
         int rc = PTK_OK;
         if (cap != 0u) {
-          PTK_WITH_EUCLID64(
-              rc = (launch_radius64_capped<M, true>(t, d_q, perm, nq, radius, e, cap, nullptr, d_offsets, d_out, nullptr, lease, rs)));
+          rc = ptkd::with_euclid64(t->metric.load(), [&](auto m) {
+            return launch_radius64_capped<ptkd::type_of<decltype(m)>, true>(t, d_q, perm, nq, radius, e, cap, nullptr,
+                d_offsets, d_out, nullptr, lease, rs);
+          });
         } else {
-          PTK_WITH_METRIC64(rc = (launch_radius64<M, true>(t, d_q, perm, nq, radius, e, nullptr, d_offsets, d_out, nullptr, lease)));
+          rc = ptkd::with_metric64(t->metric.load(), [&](auto m) {
+            return launch_radius64<ptkd::type_of<decltype(m)>, true>(t, d_q, perm, nq, radius, e, nullptr, d_offsets, d_out,
+                                                          nullptr, lease);
+          });
         }
         if (rc == PTK_OK && sort) rc = sort_rows64(nq, d_offsets, d_out);
         return rc;
@@ -1331,7 +1274,10 @@ int ptk_search64_radius_radii(const ptk_tree64* t, const double* q, uint64_t nq,
         const uint32_t* perm = nullptr;
         int rc = order_batch64(t, d_q, nq, nullptr, lease, 0, &perm);
         if (rc == PTK_OK)
-          PTK_WITH_EUCLID64(rc = (launch_radius64_radii_fill<M>(t, d_q, perm, nq, d_r, d_offsets, d_out, nullptr, lease)));
+          rc = ptkd::with_euclid64(t->metric.load(), [&](auto m) {
+            return launch_radius64_radii_fill<ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, d_r, d_offsets, d_out, nullptr,
+                lease);
+          });
         if (rc == PTK_OK && sort) rc = sort_rows64(nq, d_offsets, d_out);
         return rc;
       });

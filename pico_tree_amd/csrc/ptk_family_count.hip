@@ -85,26 +85,26 @@ int count_table(const ptk_tree* t, void** d_table, hipStream_t s) {
 
 int count_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, uint64_t max_count,
                  bool shortcut, uint64_t* d_counts, hipStream_t s) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_within<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, radius, max_count, shortcut,
-                                                                            d_counts, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_count_within<16, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, radius, max_count,
+        shortcut, d_counts, s);
+  });
 }
 
 int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
                         uint64_t max_count, bool shortcut, uint64_t* d_counts, hipStream_t s) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_within_radii<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, d_radii, max_count,
-                                                                                  shortcut, d_counts, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_count_within_radii<16, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, d_radii, max_count,
+        shortcut, d_counts, s);
+  });
 }
 
 int radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
                       const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_radius_radii_fill<16, OVF, kGenLeafB, M>(t, d_q, perm, nq, d_radii, d_offsets,
-                                                                                  d_out, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_radius_radii_fill<16, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, d_radii, d_offsets,
+        d_out, s);
+  });
 }
 
 int clamp_counts(uint64_t* d_counts, uint64_t n, uint64_t max_count, hipStream_t s) {
@@ -146,24 +146,11 @@ int count64_within(const ptk::DevTree64& dev, int metric, const ptk::CountBox64*
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = ptk::lds64_bytes(0, dev.dim);
   const uint32_t sc = shortcut ? 1u : 0u;
-  switch (metric) {
-    case PTK_METRIC_L1:
-      hipLaunchKernelGGL(ptk::count64_within_kernel<ptk::Metric64L1>, grid, block, smem, s, dev, table, d_q, perm, q0, n,
-                         radius, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    case PTK_METRIC_LPINF:
-      hipLaunchKernelGGL(ptk::count64_within_kernel<ptk::Metric64LInf>, grid, block, smem, s, dev, table, d_q, perm, q0, n,
-                         radius, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    case PTK_METRIC_LNINF:
-      hipLaunchKernelGGL(ptk::count64_within_kernel<ptk::Metric64LNInf>, grid, block, smem, s, dev, table, d_q, perm, q0, n,
-                         radius, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    default:
-      hipLaunchKernelGGL(ptk::count64_within_kernel<ptk::Metric64L2>, grid, block, smem, s, dev, table, d_q, perm, q0, n,
-                         radius, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-  }
+  ptkd::with_euclid64(metric, [&](auto m) {
+    hipLaunchKernelGGL(ptk::count64_within_kernel<ptkd::type_of<decltype(m)>>, grid, block, smem, s, dev, table, d_q, perm,
+                       q0, n, radius, max_count, sc, d_counts, stack, slots, nullptr);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -174,24 +161,11 @@ int count64_within_radii(const ptk::DevTree64& dev, int metric, const ptk::Count
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = ptk::lds64_bytes(0, dev.dim);
   const uint32_t sc = shortcut ? 1u : 0u;
-  switch (metric) {
-    case PTK_METRIC_L1:
-      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64L1>, grid, block, smem, s, dev, table, d_q, perm, q0,
-                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    case PTK_METRIC_LPINF:
-      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64LInf>, grid, block, smem, s, dev, table, d_q, perm, q0,
-                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    case PTK_METRIC_LNINF:
-      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64LNInf>, grid, block, smem, s, dev, table, d_q, perm,
-                         q0, n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-    default:
-      hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptk::Metric64L2>, grid, block, smem, s, dev, table, d_q, perm, q0,
-                         n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
-      break;
-  }
+  ptkd::with_euclid64(metric, [&](auto m) {
+    hipLaunchKernelGGL(ptk::count64_within_radii_kernel<ptkd::type_of<decltype(m)>>, grid, block, smem, s, dev, table, d_q,
+                       perm, q0, n, d_radii, max_count, sc, d_counts, stack, slots, nullptr);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }

@@ -87,19 +87,13 @@ int launch_knn_reg(const ptk_tree* t, const float* d_q, const uint32_t* perm, ui
         const uint32_t nb = (uint32_t)((n + BLOCK - 1) / BLOCK);
         const uint32_t cap_n = cap;  // (of the whole batch: the two launches share the chip)
         ptk::Task* sp = spill + (size_t)first_block * kKnnCoopSpill;
-#define PTK_LAUNCH_REG(KK)                                                                                              \
-  do {                                                                                                                  \
-    hipLaunchKernelGGL((ptk::knn_reg_kernel<KK, S, OVF, BLOCK, LEAFB, M, true>), dim3(nb), dim3(BLOCK), smem, st,        \
-                       t->dev, d_q, t->dim, perm ? perm + lo : nullptr, n, k, inv_ratio(e), d_out, cap_n, ho);          \
-    hipLaunchKernelGGL((ptk::knn_coop_kernel<KK, kKnnCoopPool, M>), dim3(cb), dim3(64), coop_smem, st, t->dev, ranges,      \
-                       d_q, t->dim, k, d_out, ho, redo_list, ptk::kMetaRedo, sp, kKnnCoopSpill);                        \
-  } while (0)
-        if (k <= 4) PTK_LAUNCH_REG(4);
-        else if (k <= 8) PTK_LAUNCH_REG(8);
-        else if (k <= 16) PTK_LAUNCH_REG(16);
-        else if (k <= 32) PTK_LAUNCH_REG(32);
-        else PTK_LAUNCH_REG(64);
-#undef PTK_LAUNCH_REG
+        ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {
+          hipLaunchKernelGGL((ptk::knn_reg_kernel<K, S, OVF, BLOCK, LEAFB, M, true>), dim3(nb), dim3(BLOCK), smem, st,
+                             t->dev, d_q, t->dim, perm ? perm + lo : nullptr, n, k, inv_ratio(e), d_out, cap_n, ho);
+          hipLaunchKernelGGL((ptk::knn_coop_kernel<K, kKnnCoopPool, M>), dim3(cb), dim3(64), coop_smem, st, t->dev, ranges,
+                             d_q, t->dim, k, d_out, ho, redo_list, ptk::kMetaRedo, sp, kKnnCoopSpill);
+          return PTK_OK;
+        });
       };
       if (n_front != 0) {
         // (a failure between fork and join must not leave the second stream working on a scratch block the next call reuses)
@@ -122,29 +116,21 @@ int launch_knn_reg(const ptk_tree* t, const float* d_q, const uint32_t* perm, ui
       } else {
         part(0, nq, ptk::kMetaHeavy, cap_rest, tasks, coop_blocks, 0u, s);
       }
-#define PTK_LAUNCH_REDO(KK)                                                                                             \
-  hipLaunchKernelGGL((ptk::knn_redo_kernel<KK, S, OVF, LEAFB, M>), dim3(t->cus), dim3(64), smem, s, t->dev, d_q, t->dim, \
-                     k, inv_ratio(e), d_out, meta, ptk::kMetaRedo, redo_list)
-      if (k <= 4) PTK_LAUNCH_REDO(4);
-      else if (k <= 8) PTK_LAUNCH_REDO(8);
-      else if (k <= 16) PTK_LAUNCH_REDO(16);
-      else if (k <= 32) PTK_LAUNCH_REDO(32);
-      else PTK_LAUNCH_REDO(64);
-#undef PTK_LAUNCH_REDO
+      ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {
+        hipLaunchKernelGGL((ptk::knn_redo_kernel<K, S, OVF, LEAFB, M>), dim3(t->cus), dim3(64), smem, s, t->dev, d_q,
+                           t->dim, k, inv_ratio(e), d_out, meta, ptk::kMetaRedo, redo_list);
+        return PTK_OK;
+      });
       PTK_HIP(hipGetLastError());
       timer.stop(0, nq);
       return PTK_OK;
     }
   }
-#define PTK_LAUNCH_REG(KK)                                                                                          \
-  hipLaunchKernelGGL((ptk::knn_reg_kernel<KK, S, OVF, BLOCK, LEAFB, M>), dim3(blocks), dim3(BLOCK), smem, s, t->dev, d_q, \
-                     t->dim, perm, nq, k, inv_ratio(e), d_out, 0u, ptk::Handover{})
-  if (k <= 4) PTK_LAUNCH_REG(4);
-  else if (k <= 8) PTK_LAUNCH_REG(8);
-  else if (k <= 16) PTK_LAUNCH_REG(16);
-  else if (k <= 32) PTK_LAUNCH_REG(32);
-  else PTK_LAUNCH_REG(64);  // (33 .. 64: knn_reg_max)
-#undef PTK_LAUNCH_REG
+  ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {  // (64 slots for 33 .. 64: knn_reg_max)
+    hipLaunchKernelGGL((ptk::knn_reg_kernel<K, S, OVF, BLOCK, LEAFB, M>), dim3(blocks), dim3(BLOCK), smem, s, t->dev, d_q,
+                       t->dim, perm, nq, k, inv_ratio(e), d_out, 0u, ptk::Handover{});
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, nq);
   return PTK_OK;
@@ -163,21 +149,15 @@ int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm,
   if (k <= 64) {
     constexpr int S = kGenRing;
     const size_t smem = (size_t)S * BLOCK * 8;
-#define PTK_LAUNCH_REG_WITHIN(KK)                                                                                       \
-  do {                                                                                                                  \
-    if constexpr (kRows)                                                                                                \
-      hipLaunchKernelGGL((ptk::knn_reg_within_radii_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK),  \
-                         smem, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.radii, r.unseeded);                        \
-    else                                                                                                                \
-      hipLaunchKernelGGL((ptk::knn_reg_within_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, \
-                         s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.seed, r.radius);                                 \
-  } while (0)
-    if (k <= 4) PTK_LAUNCH_REG_WITHIN(4);
-    else if (k <= 8) PTK_LAUNCH_REG_WITHIN(8);
-    else if (k <= 16) PTK_LAUNCH_REG_WITHIN(16);
-    else if (k <= 32) PTK_LAUNCH_REG_WITHIN(32);
-    else PTK_LAUNCH_REG_WITHIN(64);
-#undef PTK_LAUNCH_REG_WITHIN
+    ptkd::with_slots<4, 8, 16, 32, 64>(k, [&](auto K) {
+      if constexpr (kRows)
+        hipLaunchKernelGGL((ptk::knn_reg_within_radii_kernel<K, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK),
+                           smem, s, t->dev, d_q, t->dim, perm, nq, k, d_out, r.radii, r.unseeded);
+      else
+        hipLaunchKernelGGL((ptk::knn_reg_within_kernel<K, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, s,
+                           t->dev, d_q, t->dim, perm, nq, k, d_out, r.seed, r.radius);
+      return PTK_OK;
+    });
   } else {  // (the LDS budget of launch_knn)
     constexpr int S = 16;
     const size_t stack_bytes = (size_t)S * BLOCK * 8, list_bytes = (size_t)k * BLOCK * 8;
@@ -211,13 +191,9 @@ int launch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm,
 template <class R>
 int dispatch_knn_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, const R& r,
                         ptk::Neighbor* d_out, hipStream_t s) {
-  int rc = PTK_OK;
-  if (k <= 64) {
-    PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
-  } else {
-    PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn_within<OVF, M>(t, d_q, perm, nq, k, r, d_out, s))));
-  }
-  return rc;
+  return with_metric_ovf(t, k <= 64 ? kGenRing : 16, [&](auto m, auto ovf) {
+    return launch_knn_within<ovf, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, r, d_out, s);
+  });
 }
 
 static __global__ void warm_knn_kernel() {}
@@ -228,25 +204,27 @@ namespace ptkf {
 
 int knn_reg(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float e,
             ptk::Neighbor* d_out, hipStream_t s, ptkb::Scratch* scratch) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_reg<kGenRing, OVF, 64, kGenLeafB, M>(t, d_q, perm, nq, k, e, d_out, s, scratch))));
-  return rc;
+  return with_metric_ovf(t, kGenRing, [&](auto m, auto ovf) {
+    return launch_knn_reg<kGenRing, ovf, 64, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, e, d_out, s,
+        scratch);
+  });
 }
 
 int knn_rows(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, uint32_t k, float e,
              ptk::Neighbor* d_out, hipStream_t s) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_knn<16, OVF, 64, 4, M>(t, d_q, perm, nq, k, e, d_out, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_knn<16, ovf, 64, 4, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, k, e, d_out, s);
+  });
 }
 
 // One piece of a batch on a tree deeper than the private spill classes: the record stacks spill to `dev.deep_spill`.
 int knn_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float e,
              ptk::Neighbor* d_out, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  PTK_WITH_METRIC({
-    hipLaunchKernelGGL((ptk::knn_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s, dev,
-                       d_q, t->dim, nullptr, n, k, inv_ratio(e), d_out);
+  ptkd::with_metric(t->metric.load(), [&](auto m) {
+    hipLaunchKernelGGL((ptk::knn_kernel<16, -1, 64, 4, false, ptkd::type_of<decltype(m)>>), dim3(blocks), dim3(64),
+                       (size_t)16 * 64 * 8, s, dev, d_q, t->dim, nullptr, n, k, inv_ratio(e), d_out);
+    return PTK_OK;
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
@@ -266,9 +244,10 @@ int knn_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm, 
 int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k, float radius,
                     ptk::Neighbor* d_out, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  PTK_WITH_METRIC({
-    hipLaunchKernelGGL((ptk::knn_within_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s,
-                       dev, d_q, t->dim, nullptr, n, k, d_out, 3.402823466e+38f, radius);
+  ptkd::with_metric(t->metric.load(), [&](auto m) {
+    hipLaunchKernelGGL((ptk::knn_within_kernel<16, -1, 64, 4, false, ptkd::type_of<decltype(m)>>), dim3(blocks), dim3(64),
+                       (size_t)16 * 64 * 8, s, dev, d_q, t->dim, nullptr, n, k, d_out, 3.402823466e+38f, radius);
+    return PTK_OK;
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
@@ -278,9 +257,10 @@ int knn_within_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q
 int knn_within_radii_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, uint32_t k,
                           const float* d_radii, ptk::Neighbor* d_out, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  PTK_WITH_METRIC({
-    hipLaunchKernelGGL((ptk::knn_within_radii_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8,
-                       s, dev, d_q, t->dim, nullptr, n, k, d_out, d_radii, 1u);
+  ptkd::with_metric(t->metric.load(), [&](auto m) {
+    hipLaunchKernelGGL((ptk::knn_within_radii_kernel<16, -1, 64, 4, false, ptkd::type_of<decltype(m)>>), dim3(blocks),
+                       dim3(64), (size_t)16 * 64 * 8, s, dev, d_q, t->dim, nullptr, n, k, d_out, d_radii, 1u);
+    return PTK_OK;
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;

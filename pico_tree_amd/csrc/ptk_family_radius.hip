@@ -15,13 +15,11 @@ int launch_radius(const ptk_tree* t, const float* d_q, const uint32_t* perm, uin
   const uint32_t blocks = (uint32_t)((nq + BLOCK - 1) / BLOCK);
   const size_t smem = (size_t)S * BLOCK * 8;
   Timer timer(t, s);
-  if (!fill) {
-    hipLaunchKernelGGL((ptk::radius_kernel<S, OVF, BLOCK, LEAFB, false, M>), dim3(blocks), dim3(BLOCK), smem, s,
-                       t->dev, d_q, t->dim, perm, nq, radius, inv_ratio(e), d_counts, d_offsets, d_out, n_dev);
-  } else {
-    hipLaunchKernelGGL((ptk::radius_kernel<S, OVF, BLOCK, LEAFB, true, M>), dim3(blocks), dim3(BLOCK), smem, s,
-                       t->dev, d_q, t->dim, perm, nq, radius, inv_ratio(e), d_counts, d_offsets, d_out, n_dev);
-  }
+  ptkd::with_bool(fill, [&](auto FILL) {
+    hipLaunchKernelGGL((ptk::radius_kernel<S, OVF, BLOCK, LEAFB, FILL, M>), dim3(blocks), dim3(BLOCK), smem, s, t->dev, d_q,
+                       t->dim, perm, nq, radius, inv_ratio(e), d_counts, d_offsets, d_out, n_dev);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, n_dev ? 0 : nq);
   return PTK_OK;
@@ -72,37 +70,28 @@ int launch_radius_list(const ptk_tree* t, const float* d_q, const uint32_t* perm
     if (!ho.heavy_list || !ho.ntasks || !ho.tasks || !redo_list || !spill) return fail(PTK_ERR_NOMEM, "scratch block too small");
     PTK_HIP(hipMemsetAsync(heavy->meta, 0, ptk::kMetaWords * 4, s));
   }
-#define PTK_LAUNCH_LIST(BIG, EXACT)                                                                                   \
-  do {                                                                                                                \
-    if (capped)                                                                                                       \
-      hipLaunchKernelGGL((ptk::radius_list_kernel<S, OVF, LEAFB, M, BIG, EXACT, true>), dim3(cap.n_static), dim3(64),  \
-                         smem, s, t->dev, d_q, t->dim, perm, nq, radius, inv_ratio(e), d_counts, cap, far_cap, ho);    \
-    else                                                                                                              \
-      hipLaunchKernelGGL((ptk::radius_list_kernel<S, OVF, LEAFB, M, BIG, EXACT, false>), dim3(cap.n_static), dim3(64), \
-                         smem, s, t->dev, d_q, t->dim, perm, nq, radius, inv_ratio(e), d_counts, cap, 0u,              \
-                         ptk::Handover{});                                                                            \
-  } while (0)
-  if (big && exact) PTK_LAUNCH_LIST(true, true);
-  else if (big) PTK_LAUNCH_LIST(true, false);
-  else if (exact) PTK_LAUNCH_LIST(false, true);
-  else PTK_LAUNCH_LIST(false, false);
-#undef PTK_LAUNCH_LIST
+  ptkd::with_bools(big, exact, [&](auto BIG, auto EXACT) {
+    return ptkd::with_bool(capped, [&](auto CAPPED) {
+      hipLaunchKernelGGL((ptk::radius_list_kernel<S, OVF, LEAFB, M, BIG, EXACT, CAPPED>), dim3(cap.n_static), dim3(64),
+                         smem, s, t->dev, d_q, t->dim, perm, nq, radius, inv_ratio(e), d_counts, cap, CAPPED ? far_cap : 0u,
+                         CAPPED ? ho : ptk::Handover{});
+      return PTK_OK;
+    });
+  });
   PTK_HIP(hipGetLastError());
   if (capped) {
     // The queries handed over, a wavefront each (sorted leaf entries for the fill pass, the count completed); then the
     // rows that could not be finished that way, counted again from the root by one lane each.
     const size_t coop_smem = (size_t)ptk::radius_coop_lds_words(kRadiusCoopPool) * 4;
-    if (exact) {
-      int rc = allow_lds(ptk::radius_coop_count_kernel<kRadiusCoopPool, M, true>, coop_smem);
-      if (rc != PTK_OK) return rc;
-      hipLaunchKernelGGL((ptk::radius_coop_count_kernel<kRadiusCoopPool, M, true>), dim3(coop_blocks), dim3(64), coop_smem, s,
-                         t->dev, d_q, t->dim, radius, inv_ratio(e), d_counts, ho, *heavy, redo_list, spill, kRadiusCoopSpill);
-    } else {
-      int rc = allow_lds(ptk::radius_coop_count_kernel<kRadiusCoopPool, M, false>, coop_smem);
-      if (rc != PTK_OK) return rc;
-      hipLaunchKernelGGL((ptk::radius_coop_count_kernel<kRadiusCoopPool, M, false>), dim3(coop_blocks), dim3(64), coop_smem, s,
-                         t->dev, d_q, t->dim, radius, inv_ratio(e), d_counts, ho, *heavy, redo_list, spill, kRadiusCoopSpill);
-    }
+    const int rc = ptkd::with_bool(exact, [&](auto EXACT) {
+      const int lds_rc = allow_lds(ptk::radius_coop_count_kernel<kRadiusCoopPool, M, EXACT>, coop_smem);
+      if (lds_rc == PTK_OK)
+        hipLaunchKernelGGL((ptk::radius_coop_count_kernel<kRadiusCoopPool, M, EXACT>), dim3(coop_blocks), dim3(64),
+                           coop_smem, s, t->dev, d_q, t->dim, radius, inv_ratio(e), d_counts, ho, *heavy, redo_list, spill,
+                           kRadiusCoopSpill);
+      return lds_rc;
+    });
+    if (rc != PTK_OK) return rc;
     const uint32_t redo_blocks = (heavy->max_heavy + 63u) / 64u;
     hipLaunchKernelGGL((ptk::radius_kernel<S, OVF, 64, LEAFB, false, M>), dim3(redo_blocks), dim3(64), (size_t)S * 64 * 8, s,
                        t->dev, d_q, t->dim, redo_list, (uint64_t)heavy->max_heavy, radius, inv_ratio(e), d_counts, nullptr,
@@ -144,31 +133,34 @@ namespace ptkf {
 int radius_traverse(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e, bool fill,
                     uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s,
                     const uint32_t* n_dev) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_radius<16, OVF, 64, kGenLeafB, M>(t, d_q, perm, nq, radius, e, fill, d_counts, d_offsets, d_out, s, n_dev))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_radius<16, ovf, 64, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, radius, e, fill, d_counts,
+        d_offsets, d_out, s, n_dev);
+  });
 }
 
 int radius_capture(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e,
                    uint64_t* d_counts, const ptk::RadiusCapture& cap, hipStream_t s) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_radius_capture<kGenRing, OVF, 64, kGenLeafB, M>(t, d_q, perm, nq, radius, e, d_counts, cap, s))));
-  return rc;
+  return with_metric_ovf(t, kGenRing, [&](auto m, auto ovf) {
+    return launch_radius_capture<kGenRing, ovf, 64, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, radius, e,
+        d_counts, cap, s);
+  });
 }
 
 int radius_list(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius, float e,
                 uint64_t* d_counts, const ptk::RadiusCapture& cap, hipStream_t s, uint32_t far_cap, ptkb::Scratch* scratch,
                 const ptk::RadiusHeavy* heavy) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_radius_list<kGenRing, OVF, kGenLeafB, M>(t, d_q, perm, nq, radius, e, d_counts, cap, s, far_cap, scratch, heavy))));
-  return rc;
+  return with_metric_ovf(t, kGenRing, [&](auto m, auto ovf) {
+    return launch_radius_list<kGenRing, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, radius, e, d_counts,
+        cap, s, far_cap, scratch, heavy);
+  });
 }
 
 int radius_replay(const ptk_tree* t, const float* d_q, float e, const ptk::RadiusCapture& cap, const uint64_t* d_offsets,
                   ptk::Neighbor* d_out, uint32_t* over_list, uint32_t* n_over, hipStream_t s, const ptk::RadiusHeavy* heavy) {
-  int rc = PTK_OK;
-  PTK_WITH_METRIC((rc = launch_radius_replay<M>(t, d_q, e, cap, d_offsets, d_out, over_list, n_over, s, heavy)));
-  return rc;
+  return ptkd::with_metric(t->metric.load(), [&](auto m) {
+    return launch_radius_replay<ptkd::type_of<decltype(m)>>(t, d_q, e, cap, d_offsets, d_out, over_list, n_over, s, heavy);
+  });
 }
 
 // The rows of a captured log of hits (r03's form: dim > 3, PTK_RADIUS_LISTS=0) scattered to their places.
@@ -191,13 +183,13 @@ int radius_log_scatter(const ptk_tree* t, const ptk::RadiusCapture& cap, const u
 int radius_deep(const ptk_tree* t, const ptk::DevTree& dev, const float* d_q, uint64_t n, float radius, float e, bool fill,
                 uint64_t* d_counts, const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
-  PTK_WITH_METRIC({
-    if (fill)
-      hipLaunchKernelGGL((ptk::radius_kernel<16, -1, 64, 4, true, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s, dev,
-                         d_q, t->dim, nullptr, n, radius, inv_ratio(e), d_counts, d_offsets, d_out, nullptr);
-    else
-      hipLaunchKernelGGL((ptk::radius_kernel<16, -1, 64, 4, false, M>), dim3(blocks), dim3(64), (size_t)16 * 64 * 8, s, dev,
-                         d_q, t->dim, nullptr, n, radius, inv_ratio(e), d_counts, d_offsets, d_out, nullptr);
+  ptkd::with_metric(t->metric.load(), [&](auto m) {
+    return ptkd::with_bool(fill, [&](auto FILL) {
+      hipLaunchKernelGGL((ptk::radius_kernel<16, -1, 64, 4, FILL, ptkd::type_of<decltype(m)>>), dim3(blocks), dim3(64),
+                         (size_t)16 * 64 * 8, s, dev, d_q, t->dim, nullptr, n, radius, inv_ratio(e), d_counts, d_offsets,
+                         d_out, nullptr);
+      return PTK_OK;
+    });
   });
   PTK_HIP(hipGetLastError());
   return PTK_OK;

@@ -21,15 +21,11 @@ int launch_knn_self(const ptk_tree* t, uint64_t first, uint64_t n, uint32_t k, p
   const uint32_t blocks = (uint32_t)((n + BLOCK - 1) / BLOCK);
   const size_t smem = (size_t)S * BLOCK * 8;
   Timer timer(t, s);
-#define PTK_LAUNCH_SELF(KK)                                                                                         \
-  hipLaunchKernelGGL((ptk::knn_self_kernel<KK, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, s, t->dev, \
-                     t->dim, first, n, k, d_out)
-  if (k + 1 <= 4) PTK_LAUNCH_SELF(4);
-  else if (k + 1 <= 8) PTK_LAUNCH_SELF(8);
-  else if (k + 1 <= 16) PTK_LAUNCH_SELF(16);
-  else if (k + 1 <= 32) PTK_LAUNCH_SELF(32);
-  else PTK_LAUNCH_SELF(64);
-#undef PTK_LAUNCH_SELF
+  ptkd::with_slots<4, 8, 16, 32, 64>(k + 1, [&](auto K) {
+    hipLaunchKernelGGL((ptk::knn_self_kernel<K, S, OVF, BLOCK, kGenLeafB, M>), dim3(blocks), dim3(BLOCK), smem, s, t->dev,
+                       t->dim, first, n, k, d_out);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, n);
   return PTK_OK;
@@ -42,12 +38,12 @@ int launch_count_self(const ptk_tree* t, uint64_t first, uint64_t n, float radiu
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
   const auto* table = static_cast<const ptk::CountBox*>(t->d_count_table);
   Timer timer(t, s);
-  if (d_radii != nullptr)
-    hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
-                       t->dev, table, t->dim, first, n, radius, d_radii, max_count, shortcut ? 1u : 0u, d_counts, nullptr);
-  else
-    hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
-                       t->dev, table, t->dim, first, n, radius, d_radii, max_count, shortcut ? 1u : 0u, d_counts, nullptr);
+  ptkd::with_bool(d_radii != nullptr, [&](auto PER_ROW) {
+    hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, PER_ROW, M>), dim3(blocks), dim3(64),
+                       (size_t)S * 64 * 8, s, t->dev, table, t->dim, first, n, radius, d_radii, max_count,
+                       shortcut ? 1u : 0u, d_counts, nullptr);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, n);
   return PTK_OK;
@@ -58,12 +54,11 @@ int launch_radius_self_fill(const ptk_tree* t, uint64_t first, uint64_t n, float
                             const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
   const uint32_t blocks = (uint32_t)((n + 63) / 64);
   Timer timer(t, s);
-  if (d_radii != nullptr)
-    hipLaunchKernelGGL((ptk::radius_self_fill_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64),
+  ptkd::with_bool(d_radii != nullptr, [&](auto PER_ROW) {
+    hipLaunchKernelGGL((ptk::radius_self_fill_kernel<S, OVF, 64, kGenLeafB, PER_ROW, M>), dim3(blocks), dim3(64),
                        (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, d_offsets, d_out);
-  else
-    hipLaunchKernelGGL((ptk::radius_self_fill_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64),
-                       (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, d_offsets, d_out);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, n);
   return PTK_OK;
@@ -75,12 +70,11 @@ int launch_count64_self(const ptk::DevTree64& dev, const ptk::CountBox64* table,
                         uint32_t slots, hipStream_t s) {
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = ptk::lds64_bytes(0, dev.dim);
-  if (d_radii != nullptr)
-    hipLaunchKernelGGL((ptk::count64_self_kernel<M, true>), grid, block, smem, s, dev, table, first, n, radius, d_radii,
+  ptkd::with_bool(d_radii != nullptr, [&](auto PER_ROW) {
+    hipLaunchKernelGGL((ptk::count64_self_kernel<M, PER_ROW>), grid, block, smem, s, dev, table, first, n, radius, d_radii,
                        max_count, shortcut ? 1u : 0u, d_counts, stack, slots, nullptr);
-  else
-    hipLaunchKernelGGL((ptk::count64_self_kernel<M, false>), grid, block, smem, s, dev, table, first, n, radius, d_radii,
-                       max_count, shortcut ? 1u : 0u, d_counts, stack, slots, nullptr);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -91,12 +85,11 @@ int launch_radius64_self_fill(const ptk::DevTree64& dev, uint64_t first, uint64_
                               hipStream_t s) {
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = ptk::lds64_bytes(0, dev.dim);
-  if (d_radii != nullptr)
-    hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, true>), grid, block, smem, s, dev, first, n, radius, d_radii,
+  ptkd::with_bool(d_radii != nullptr, [&](auto PER_ROW) {
+    hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, PER_ROW>), grid, block, smem, s, dev, first, n, radius, d_radii,
                        d_offsets, d_out, stack, slots);
-  else
-    hipLaunchKernelGGL((ptk::radius64_self_fill_kernel<M, false>), grid, block, smem, s, dev, first, n, radius, d_radii,
-                       d_offsets, d_out, stack, slots);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -109,31 +102,20 @@ int launch_cluster_self(const ptk_tree* t, int pass, uint64_t first, uint64_t n,
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = (size_t)S * 64 * 8;
   const auto* table = static_cast<const ptk::CountBox*>(t->d_count_table);
-  const bool per_row = d_radii != nullptr;
   Timer timer(t, s);
-#define PTK_CLUSTER_LINK(PER_ROW, COMPRESS)                                                                               \
-  hipLaunchKernelGGL((ptk::cluster_link_kernel<S, OVF, 64, kGenLeafB, PER_ROW, COMPRESS, M>), grid, block, smem, s, t->dev, \
-                     t->dim, first, n, radius, d_radii, d_labels)
-  if (pass == ptkf::kClusterMark) {
-    if (per_row)
-      hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, true, M, ptk::ClusterMarkStore>), grid, block, smem, s,
-                         t->dev, table, t->dim, first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, nullptr);
+  ptkd::with_bools(d_radii != nullptr, compress, [&](auto PER_ROW, auto COMPRESS) {
+    if (pass == ptkf::kClusterMark)
+      hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, PER_ROW, M, ptk::ClusterMarkStore>), grid, block,
+                         smem, s, t->dev, table, t->dim, first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u,
+                         d_labels, nullptr);
+    else if (pass == ptkf::kClusterLink)
+      hipLaunchKernelGGL((ptk::cluster_link_kernel<S, OVF, 64, kGenLeafB, PER_ROW, COMPRESS, M>), grid, block, smem, s,
+                         t->dev, t->dim, first, n, radius, d_radii, d_labels);
     else
-      hipLaunchKernelGGL((ptk::count_self_kernel<S, OVF, 64, kGenLeafB, false, M, ptk::ClusterMarkStore>), grid, block, smem, s,
-                         t->dev, table, t->dim, first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, nullptr);
-  } else if (pass == ptkf::kClusterLink) {
-    if (per_row && compress) PTK_CLUSTER_LINK(true, true);
-    else if (per_row) PTK_CLUSTER_LINK(true, false);
-    else if (compress) PTK_CLUSTER_LINK(false, true);
-    else PTK_CLUSTER_LINK(false, false);
-  } else if (per_row) {
-    hipLaunchKernelGGL((ptk::cluster_border_kernel<S, OVF, 64, kGenLeafB, true, M>), grid, block, smem, s, t->dev, t->dim,
-                       first, n, radius, d_radii, d_labels);
-  } else {
-    hipLaunchKernelGGL((ptk::cluster_border_kernel<S, OVF, 64, kGenLeafB, false, M>), grid, block, smem, s, t->dev, t->dim,
-                       first, n, radius, d_radii, d_labels);
-  }
-#undef PTK_CLUSTER_LINK
+      hipLaunchKernelGGL((ptk::cluster_border_kernel<S, OVF, 64, kGenLeafB, PER_ROW, M>), grid, block, smem, s, t->dev,
+                         t->dim, first, n, radius, d_radii, d_labels);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(pass == ptkf::kClusterLink ? 3 : 0, n);
   return PTK_OK;
@@ -145,30 +127,18 @@ int launch_cluster64_self(const ptk::DevTree64& dev, const ptk::CountBox64* tabl
                           int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
   const dim3 grid((uint32_t)((n + 63) / 64)), block(64);
   const size_t smem = ptk::lds64_bytes(0, dev.dim);
-  const bool per_row = d_radii != nullptr;
-#define PTK_CLUSTER64_LINK(PER_ROW, COMPRESS)                                                                          \
-  hipLaunchKernelGGL((ptk::cluster64_link_kernel<M, PER_ROW, COMPRESS>), grid, block, smem, s, dev, first, n, radius, \
-                     d_radii, d_labels, stack, slots)
-  if (pass == ptkf::kClusterMark) {
-    if (per_row)
-      hipLaunchKernelGGL((ptk::count64_self_kernel<M, true, ptk::ClusterMarkStore>), grid, block, smem, s, dev, table, first, n,
-                         radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, stack, slots, nullptr);
+  ptkd::with_bools(d_radii != nullptr, compress, [&](auto PER_ROW, auto COMPRESS) {
+    if (pass == ptkf::kClusterMark)
+      hipLaunchKernelGGL((ptk::count64_self_kernel<M, PER_ROW, ptk::ClusterMarkStore>), grid, block, smem, s, dev, table,
+                         first, n, radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, stack, slots, nullptr);
+    else if (pass == ptkf::kClusterLink)
+      hipLaunchKernelGGL((ptk::cluster64_link_kernel<M, PER_ROW, COMPRESS>), grid, block, smem, s, dev, first, n, radius,
+                         d_radii, d_labels, stack, slots);
     else
-      hipLaunchKernelGGL((ptk::count64_self_kernel<M, false, ptk::ClusterMarkStore>), grid, block, smem, s, dev, table, first, n,
-                         radius, d_radii, min_neighbors, shortcut ? 1u : 0u, d_labels, stack, slots, nullptr);
-  } else if (pass == ptkf::kClusterLink) {
-    if (per_row && compress) PTK_CLUSTER64_LINK(true, true);
-    else if (per_row) PTK_CLUSTER64_LINK(true, false);
-    else if (compress) PTK_CLUSTER64_LINK(false, true);
-    else PTK_CLUSTER64_LINK(false, false);
-  } else if (per_row) {
-    hipLaunchKernelGGL((ptk::cluster64_border_kernel<M, true>), grid, block, smem, s, dev, first, n, radius, d_radii, d_labels,
-                       stack, slots);
-  } else {
-    hipLaunchKernelGGL((ptk::cluster64_border_kernel<M, false>), grid, block, smem, s, dev, first, n, radius, d_radii, d_labels,
-                       stack, slots);
-  }
-#undef PTK_CLUSTER64_LINK
+      hipLaunchKernelGGL((ptk::cluster64_border_kernel<M, PER_ROW>), grid, block, smem, s, dev, first, n, radius, d_radii,
+                         d_labels, stack, slots);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
@@ -182,12 +152,12 @@ int launch_frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radi
   const uint32_t has_view = view != nullptr ? 1u : 0u;
   const float vx = view != nullptr ? view[0] : 0.0f, vy = view != nullptr ? view[1] : 0.0f, vz = view != nullptr ? view[2] : 0.0f;
   Timer timer(t, s);
-  if (d_radii != nullptr)
-    hipLaunchKernelGGL((ptk::frames_self_kernel<S, OVF, 64, kGenLeafB, true, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
-                       t->dev, t->dim, first, n, radius, d_radii, min_neighbors, has_view, vx, vy, vz, d_frames, d_moments);
-  else
-    hipLaunchKernelGGL((ptk::frames_self_kernel<S, OVF, 64, kGenLeafB, false, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
-                       t->dev, t->dim, first, n, radius, d_radii, min_neighbors, has_view, vx, vy, vz, d_frames, d_moments);
+  ptkd::with_bool(d_radii != nullptr, [&](auto PER_ROW) {
+    hipLaunchKernelGGL((ptk::frames_self_kernel<S, OVF, 64, kGenLeafB, PER_ROW, M>), dim3(blocks), dim3(64),
+                       (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, min_neighbors, has_view, vx, vy,
+                       vz, d_frames, d_moments);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, n);
   return PTK_OK;
@@ -201,9 +171,9 @@ namespace ptkf {
 
 int knn_self(const ptk_tree* t, uint64_t first, uint64_t n, uint32_t k, ptk::Neighbor* d_out, hipStream_t s) {
   if (k + 1 > 64u || t->dim > 3) return fail(PTK_ERR_INVALID, "knn_self: not a call of the direct kernel");
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(kGenRing, (launch_knn_self<OVF, M>(t, first, n, k, d_out, s))));
-  return rc;
+  return with_metric_ovf(t, kGenRing, [&](auto m, auto ovf) {
+    return launch_knn_self<ovf, ptkd::type_of<decltype(m)>>(t, first, n, k, d_out, s);
+  });
 }
 
 int self_queries(const float4* recs, const float* pts, uint32_t stride, uint32_t dim, uint64_t first, uint64_t n, float* d_q,
@@ -240,89 +210,76 @@ int drop_self64(const void* rows, const int32_t* index, uint64_t first, uint64_t
 int count_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t max_count,
                bool shortcut, uint64_t* d_counts, hipStream_t s) {
   if (t->dim > 3) return fail(PTK_ERR_INVALID, "count_self: not a call of the self kernels");
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_count_self<16, OVF, M>(t, first, n, radius, d_radii, max_count, shortcut, d_counts, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_count_self<16, ovf, ptkd::type_of<decltype(m)>>(t, first, n, radius, d_radii, max_count, shortcut,
+        d_counts, s);
+  });
 }
 
 int radius_self_fill(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
                      const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s) {
   if (t->dim > 3) return fail(PTK_ERR_INVALID, "radius_self_fill: not a call of the self kernels");
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_radius_self_fill<16, OVF, M>(t, first, n, radius, d_radii, d_offsets, d_out, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_radius_self_fill<16, ovf, ptkd::type_of<decltype(m)>>(t, first, n, radius, d_radii, d_offsets, d_out, s);
+  });
 }
 
 int count64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, uint64_t first, uint64_t n,
                  double radius, const double* d_radii, uint64_t max_count, bool shortcut, uint64_t* d_counts,
                  ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
-  switch (metric) {
-    case PTK_METRIC_L1:
-      return launch_count64_self<ptk::Metric64L1>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
-    case PTK_METRIC_LPINF:
-      return launch_count64_self<ptk::Metric64LInf>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
-    case PTK_METRIC_LNINF:
-      return launch_count64_self<ptk::Metric64LNInf>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
-    default:
-      return launch_count64_self<ptk::Metric64L2>(dev, table, first, n, radius, d_radii, max_count, shortcut, d_counts, stack, slots, s);
-  }
+  return ptkd::with_euclid64(metric, [&](auto m) {
+    return launch_count64_self<ptkd::type_of<decltype(m)>>(dev, table, first, n, radius, d_radii, max_count, shortcut,
+                                                      d_counts, stack, slots, s);
+  });
 }
 
 int radius64_self_fill(const ptk::DevTree64& dev, int metric, uint64_t first, uint64_t n, double radius, const double* d_radii,
                        const uint64_t* d_offsets, void* d_out, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
   auto* o = static_cast<ptk::Neighbor64*>(d_out);
-  switch (metric) {
-    case PTK_METRIC_L1:
-      return launch_radius64_self_fill<ptk::Metric64L1>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
-    case PTK_METRIC_LPINF:
-      return launch_radius64_self_fill<ptk::Metric64LInf>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
-    case PTK_METRIC_LNINF:
-      return launch_radius64_self_fill<ptk::Metric64LNInf>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
-    default:
-      return launch_radius64_self_fill<ptk::Metric64L2>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots, s);
-  }
+  return ptkd::with_euclid64(metric, [&](auto m) {
+    return launch_radius64_self_fill<ptkd::type_of<decltype(m)>>(dev, first, n, radius, d_radii, d_offsets, o, stack, slots,
+                                                            s);
+  });
 }
 
 int cluster_self(const ptk_tree* t, int pass, uint64_t first, uint64_t n, float radius, const float* d_radii,
                  uint64_t min_neighbors, bool shortcut, bool compress, int32_t* d_labels, hipStream_t s) {
   if (t->dim > 3) return fail(PTK_ERR_INVALID, "cluster_self: not a call of the self kernels");
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_cluster_self<16, OVF, M>(t, pass, first, n, radius, d_radii, min_neighbors, shortcut,
-                                                                   compress, d_labels, s))));
-  return rc;
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_cluster_self<16, ovf, ptkd::type_of<decltype(m)>>(t, pass, first, n, radius, d_radii, min_neighbors,
+        shortcut, compress, d_labels, s);
+  });
 }
 
 int cluster64_self(const ptk::DevTree64& dev, int metric, const ptk::CountBox64* table, int pass, uint64_t first, uint64_t n,
                    double radius, const double* d_radii, uint64_t min_neighbors, bool shortcut, bool compress,
                    int32_t* d_labels, ptk::Rec64* stack, uint32_t slots, hipStream_t s) {
-#define PTK_CLUSTER64(M) \
-  launch_cluster64_self<M>(dev, table, pass, first, n, radius, d_radii, min_neighbors, shortcut, compress, d_labels, stack, slots, s)
-  switch (metric) {
-    case PTK_METRIC_L1: return PTK_CLUSTER64(ptk::Metric64L1);
-    case PTK_METRIC_LPINF: return PTK_CLUSTER64(ptk::Metric64LInf);
-    case PTK_METRIC_LNINF: return PTK_CLUSTER64(ptk::Metric64LNInf);
-    default: return PTK_CLUSTER64(ptk::Metric64L2);
-  }
-#undef PTK_CLUSTER64
+  return ptkd::with_euclid64(metric, [&](auto m) {
+    return launch_cluster64_self<ptkd::type_of<decltype(m)>>(dev, table, pass, first, n, radius, d_radii, min_neighbors,
+                                                            shortcut, compress, d_labels, stack, slots, s);
+  });
 }
 
 int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t min_neighbors,
                 const float* view, ptk_frame* d_frames, ptk_moments* d_moments, hipStream_t s) {
   static_assert(sizeof(ptk_frame) == sizeof(ptk::lf::frame3) && sizeof(ptk_moments) == sizeof(ptk::lf::moments3), "record layout");
   if (t->dim != 3) return fail(PTK_ERR_INVALID, "frames_self: not a call of the frames kernel");
-  auto* f = reinterpret_cast<ptk::lf::frame3*>(d_frames);
-  auto* m = reinterpret_cast<ptk::lf::moments3*>(d_moments);
-  int rc = PTK_OK;
-  PTK_WITH_METRIC(PTK_WITH_OVF(16, (launch_frames_self<16, OVF, M>(t, first, n, radius, d_radii, min_neighbors, view, f, m, s))));
-  return rc;
+  auto* frames = reinterpret_cast<ptk::lf::frame3*>(d_frames);
+  auto* moments = reinterpret_cast<ptk::lf::moments3*>(d_moments);
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_frames_self<16, ovf, ptkd::type_of<decltype(m)>>(t, first, n, radius, d_radii, min_neighbors, view, frames,
+                                                                  moments, s);
+  });
 }
 
 int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, hipStream_t s) {
   const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
   if (pass == kClusterInit) hipLaunchKernelGGL(ptk::cluster_init_kernel, grid, block, 0, s, n, d_labels);
   else if (pass == kClusterDecode) hipLaunchKernelGGL(ptk::cluster_decode_kernel, grid, block, 0, s, n, d_labels);
-  else if (compress) hipLaunchKernelGGL(ptk::cluster_flatten_kernel<true>, grid, block, 0, s, n, d_labels);
-  else hipLaunchKernelGGL(ptk::cluster_flatten_kernel<false>, grid, block, 0, s, n, d_labels);
+  else ptkd::with_bool(compress, [&](auto COMPRESS) {
+    hipLaunchKernelGGL(ptk::cluster_flatten_kernel<COMPRESS>, grid, block, 0, s, n, d_labels);
+    return PTK_OK;
+  });
   PTK_HIP(hipGetLastError());
   return PTK_OK;
 }
