@@ -586,6 +586,7 @@ int emu_set_outer(void* h, const ptk_node* nodes, uint64_t n_nodes, uint64_t n_p
 
 
 uint32_t emu_max_depth(void* h) { return static_cast<Emu*>(h)->st.max_depth; }
+uint32_t emu_max_leaf_count(void* h) { return static_cast<Emu*>(h)->st.max_leaf_count; }
 
 // small_stack != 0 runs the smallest LDS ring (4 slots), so nearly every record
 // takes the spill / refill path; otherwise the shipped geometries are used.
@@ -1366,6 +1367,7 @@ void* emu64_create(const double* points, uint64_t n, uint32_t dim, uint64_t max_
 }
 void emu64_destroy(void* h) { delete static_cast<Emu64*>(h); }
 uint32_t emu64_max_depth(void* h) { return static_cast<Emu64*>(h)->st.max_depth; }
+uint32_t emu64_max_leaf_count(void* h) { return static_cast<Emu64*>(h)->st.max_leaf_count; }
 void emu64_set_metric(void* h, int metric) { static_cast<Emu64*>(h)->metric = metric; }
 
 // The kd_tree::save stream of the tree (pico_tree/internal/stream.hpp); returns its size.

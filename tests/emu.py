@@ -220,6 +220,12 @@ class EmulatedTree:
         """Depth of the encoded tree (of its k = 1 view after ``use_pile_view``)."""
         return int(self.lib.emu_max_depth(self.h))
 
+    def max_leaf_count(self):
+        """Points of the largest leaf of the encoded tree: what the count bits of its leaf references are sized from."""
+        self.lib.emu_max_leaf_count.restype = c_uint32
+        self.lib.emu_max_leaf_count.argtypes = [c_void_p]
+        return int(self.lib.emu_max_leaf_count(self.h))
+
     def two_phase_knn1(self, q, e=None, perm=None, variant=5, p2_cap=None):
         """Returns (result (nq,1), number of continuations handed to phase 2).  ``p2_cap``: far children a query of a
         capped variant may enter in phase 2 instead of the variant's own 1 - 3; ``last_p2_high_water`` = the most
@@ -359,6 +365,11 @@ class EmulatedTree64:
         self.lib.emu64_max_depth.restype = c_uint32
         self.lib.emu64_max_depth.argtypes = [c_void_p]
         return int(self.lib.emu64_max_depth(self.h))
+
+    def max_leaf_count(self):
+        self.lib.emu64_max_leaf_count.restype = c_uint32
+        self.lib.emu64_max_leaf_count.argtypes = [c_void_p]
+        return int(self.lib.emu64_max_leaf_count(self.h))
 
     def save_bytes(self) -> bytes:
         size = self.lib.emu64_save(self.h, None, 0)

@@ -28,7 +28,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases
+from tests import depth_cases, leaf_cases
 from tests import test_radius_self as rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -508,6 +508,23 @@ def test_emulated_kernels_equal_the_expected_labels(emu_lib, kind, metric):
     radii = c.radii()
     for mn, piece, compress in ((0, 647, 0), (4, 647, 1), (4, 0, 0)):
         assert np.array_equal(emu_labels(emu, radii, mn, piece, 1, compress), want_radii(c, mn)), (kind, metric, mn)
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_kernels_where_the_leaf_scan_changes(emu_lib, L):
+    """The CPU half of tests/test_leaf_boundaries.py for these kernels: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points; at the radius that holds the whole leaf its points are one cluster."""
+    pts, blob, q, nb, ref, radii = leaf_cases.case(L)
+    pts = np.asarray(pts)
+    emu = rs.Emulated(emu_lib, pts, L, "L2Squared")
+    leaf_cases.assert_leaf(emu.host, L)
+    for r in leaf_cases.self_radii(L, radii):
+        rows = leaf_cases.self_rows(ref, pts, r)
+        for mn, piece, sc, compress in ((0, 647, 1, 1), (2, 0, 1, 0), (2, 647, 0, 1)):
+            got = emu_labels(emu, r, mn, piece, sc, compress)
+            assert np.array_equal(got, expected_labels(*rows, mn)), (L, r, mn, piece)
+        if r == radii[1]:
+            assert len(np.unique(got[len(pts) - L:])) == 1 and got[-1] >= 0
 
 
 @needs_reference64

@@ -18,7 +18,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases
+from tests import depth_cases, leaf_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -142,11 +142,13 @@ def emu_count(tmp_path_factory):
 _EMU_METRIC = {"L2Squared": 0, "L1": 1, "LPInf": 2, "LNInf": 3}
 
 
-def emu_counts(lib, p, leaf, metric, q, r, max_count=0, shortcut=1, tree_points=None):
+def emu_counts(lib, p, leaf, metric, q, r, max_count=0, shortcut=1, tree_points=None, largest_leaf=None):
     """Counts of the emulated kernel; `tree_points`: build the tree over these and search it over `p` (a stream that
-    does not belong to its points)."""
+    does not belong to its points); `largest_leaf`: what the tree handed to the emulator must say of its largest leaf."""
     host = pt.KdTree(p if tree_points is None else tree_points, getattr(pt.Metric, metric), leaf,
                      device=pt.PTK_DEVICE_NONE)
+    if largest_leaf is not None:
+        leaf_cases.assert_leaf(host, largest_leaf)
     nodes, idx, _, _ = host.flat()
     h = lib.emu_create(p.ctypes.data, len(p), p.shape[1], nodes.ctypes.data, len(nodes), idx.ctypes.data)
     assert h
@@ -211,6 +213,22 @@ def test_emulated_kernel_where_the_stack_class_changes(emu_count, dim, leaf, met
         # the max and min metrics the traversal prunes by a SUM over the axes, as the reference's does)
         assert at_corner == [0, len(pts) - 3_000, 0, len(pts)], at_corner
         assert depth_cases.need(depth) - peak <= 8, peak
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_kernel_where_the_leaf_scan_changes(emu_count, L):
+    """The CPU half of tests/test_leaf_boundaries.py for the count kernel: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points (the count bits of the leaf reference go 5 -> 6 -> 7), radii that hold a part of that leaf, all of
+    it, nothing and the whole tree."""
+    pts, blob, q, nb, ref, rs_ = leaf_cases.case(L)
+    for r in rs_:
+        want = expected(ref, q, r)
+        for mc in (0, 16):
+            got, _ = emu_counts(emu_count, np.asarray(pts), L, "L2Squared", q, r, mc, largest_leaf=L)
+            assert np.array_equal(got, np.minimum(want, mc) if mc else want), (L, r, mc)
+        got, _ = emu_counts(emu_count, np.asarray(pts), L, "L2Squared", q, r, 0, shortcut=0, largest_leaf=L)
+        assert np.array_equal(got, want), (L, r, "no shortcut")
+    assert int(want[0]) == len(pts)  # (the last radius holds the whole tree)
 
 
 @needs_reference

@@ -26,7 +26,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases, poison
+from tests import depth_cases, leaf_cases, poison
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -231,11 +231,14 @@ def emu_self(tmp_path_factory):
     return lib
 
 
-def emu_rows(lib, p, leaf, metric, k, route, piece=0, ranges=None):
+def emu_rows(lib, p, leaf, metric, k, route, piece=0, ranges=None, largest_leaf=None):
     """(rows n x k, the original indices whose rows were computed): the emulated route over the leaf positions of
-    `ranges` (default: all of them).  Rows nobody computed keep the 0xA5 fill."""
+    `ranges` (default: all of them).  Rows nobody computed keep the 0xA5 fill.  `largest_leaf`: what the tree handed to
+    the emulator must say of its largest leaf."""
     p = np.ascontiguousarray(p)
     host = pt.KdTree(p, getattr(pt.Metric, metric), leaf, device=pt.PTK_DEVICE_NONE)
+    if largest_leaf is not None:
+        leaf_cases.assert_leaf(host, largest_leaf)
     nodes, idx, _, _ = host.flat()
     h = lib.emu_create(p.ctypes.data, len(p), p.shape[1], nodes.ctypes.data, len(nodes), idx.ctypes.data)
     assert h
@@ -316,6 +319,19 @@ def test_emulated_kernels_where_the_stack_class_changes(emu_self, dim, leaf, met
             got, rows = run(emu_rows, emu_self, pts, leaf, metric, k, route, 0, [(lo, hi)])
             assert len(rows) == hi - lo and np.all(np.isin(np.arange(3_000, len(pts)), rows))
             assert got[rows].tobytes() == want[rows].tobytes(), (k, route)
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_kernels_where_the_leaf_scan_changes(emu_self, L):
+    """The CPU half of tests/test_leaf_boundaries.py for these kernels: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points, the direct kernel and the staged route in pieces."""
+    pts, blob, q, nb, ref, _ = leaf_cases.case(L)
+    pts = np.asarray(pts)
+    for k in (7, 40):
+        want = expected(ref, pts, k)
+        for route, piece in ((1, 0), (2, 647)):
+            got, _ = emu_rows(emu_self, pts, L, "L2Squared", k, route, piece, largest_leaf=L)
+            assert got.tobytes() == want.tobytes(), (L, k, route)
 
 
 # ---- the C++ members (tests/cpp/knn_self_main.cpp) -------------------------------------------------------------------

@@ -20,7 +20,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases
+from tests import depth_cases, leaf_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -154,8 +154,11 @@ def emu_within(tmp_path_factory):
     return lib
 
 
-def emu_rows(lib, p, leaf, metric, q, k, r, form):
+def emu_rows(lib, p, leaf, metric, q, k, r, form, largest_leaf=None):
+    """Rows of the emulated kernel; `largest_leaf`: what the tree handed to the emulator must say of its largest leaf."""
     host = pt.KdTree(p, getattr(pt.Metric, metric), leaf, device=pt.PTK_DEVICE_NONE)
+    if largest_leaf is not None:
+        leaf_cases.assert_leaf(host, largest_leaf)
     nodes, idx, _, _ = host.flat()
     h = lib.emu_create(p.ctypes.data, len(p), p.shape[1], nodes.ctypes.data, len(nodes), idx.ctypes.data)
     assert h
@@ -226,6 +229,20 @@ def test_emulated_bounded_kernels_where_the_stack_class_changes(emu_within, dim,
     if metric in ("L2Squared", "L1"):
         # (the sum metrics: the corner queries walk the whole chain; the last radius, 1e4, reaches the cloud as well)
         assert depth_cases.need(depth) - peak <= 8, peak
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_bounded_kernels_where_the_leaf_scan_changes(emu_within, L):
+    """The CPU half of tests/test_leaf_boundaries.py for these kernels: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points (the count bits of the leaf reference go 5 -> 6 -> 7), radii that hold a part of that leaf, all of
+    it, nothing and the whole tree."""
+    pts, blob, q, nb, ref, rs_ = leaf_cases.case(L)
+    for r in rs_:
+        for k in (5, 80):
+            want = expected(ref, q, k, r)
+            for form in ((0, 1, 2) if k <= 64 else (1, 2)):
+                got = emu_rows(emu_within, np.asarray(pts), L, "L2Squared", q, k, r, form, largest_leaf=L)
+                assert got.tobytes() == want.tobytes(), (L, k, r, form)
 
 
 # ---- the C++ members (tests/cpp/knn_within_main.cpp) ----------------------------------------------------------------

@@ -30,7 +30,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases, poison
+from tests import depth_cases, leaf_cases, poison
 from tests.test_radius_self import Case, case, cloud, guarded, guards_intact, row_ids, without_self  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -299,6 +299,28 @@ def test_host_loop_and_emulated_kernel(emu_lib, kind, metric):
     assert same(emu.normals(r, 12, VIEW, want="frames")[0], hf) and same(emu.normals(r, 12, VIEW, want="moments")[1], want)
     assert same(host_normals(emu.host, r, 12, VIEW, want="frames")[0], hf)
     assert same(host_normals(emu.host, r, 12, VIEW, want="moments")[1], want)
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_kernel_where_the_leaf_scan_changes(emu_lib, L):
+    """The CPU half of tests/test_leaf_boundaries.py for this kernel: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points; the contract's moments on the reference's rows, the host loop's frames, checks (b) and (c)."""
+    pts, blob, q, nb, ref, radii = leaf_cases.case(L)
+    pts = np.asarray(pts)
+    emu = Emulated(emu_lib, pts, L, "L2Squared")
+    leaf_cases.assert_leaf(emu.host, L)
+    for r in leaf_cases.self_radii(L, radii):
+        want = expected_moments(pts, *leaf_cases.self_rows(ref, pts, r))
+        hf, hm = host_normals(emu.host, r, 2, VIEW)
+        assert same(hm, want), (L, r)
+        for piece in (0, 1000):
+            ef, em = emu.normals(r, 2, VIEW, piece=piece)
+            assert same(em, want) and same(ef, hf), (L, r, piece)
+        check_frames(hf, want, pts, VIEW, 2, ("leaf", L, r))
+        if r == 0:  # (no neighbours: no frame anywhere)
+            assert not np.isfinite(hf["curvature"]).any(), L
+        if r == radii[1]:  # (r_all: every blob point's row is the rest of the blob, and it has a frame)
+            assert np.isfinite(ef["curvature"][-L:]).all(), L
 
 
 def test_ties_give_zero_offsets_and_zero_covariances():

@@ -30,7 +30,7 @@ import pytest
 import oracle
 import pico_tree_amd as pt
 from pico_tree_amd import datasets as ds
-from tests import depth_cases, poison
+from tests import depth_cases, leaf_cases, poison
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -540,6 +540,27 @@ def test_emulated_kernels_equal_the_reference_rows_without_self(emu_lib, kind, m
     for sort in (0, 1):
         got_off, got = emu.rows(radii, clamp(want[0], 0), sort, 647)
         check_rows(got_off, got, c.want_per_row(sort), sort, (kind, metric, "per row", sort))
+
+
+@pytest.mark.parametrize("L", leaf_cases.SMALL_LEAVES)
+def test_emulated_kernels_where_the_leaf_scan_changes(emu_lib, L):
+    """The CPU half of tests/test_leaf_boundaries.py for these kernels: a tree whose largest leaf has exactly 31 | 32 | 33
+    and 64 | 65 points (the count bits of the leaf reference go 5 -> 6 -> 7); radii that hold a part of that leaf from
+    its own points, all of it, and nothing."""
+    pts, blob, q, nb, ref, radii = leaf_cases.case(L)
+    pts = np.asarray(pts)
+    emu = Emulated(emu_lib, pts, L, "L2Squared")
+    leaf_cases.assert_leaf(emu.host, L)
+    for r in leaf_cases.self_radii(L, radii):
+        want = leaf_cases.self_rows(ref, pts, r)
+        counts = clamp(want[0], 0)
+        assert r != radii[1] or np.all(counts[len(pts) - L:] == L - 1)  # (r_all: every blob point's row is the blob)
+        for mc, sc, piece in ((0, 1, 0), (7, 1, 647), (0, 0, 647)):
+            got, _ = emu.counts(r, mc, sc, piece)
+            assert np.array_equal(got, np.minimum(counts, mc) if mc else counts), (L, r, mc, sc)
+        for sort, piece in ((0, 647), (1, 0)):
+            got_off, got = emu.rows(r, counts, sort, piece)
+            check_rows(got_off, got, leaf_cases.self_rows(ref, pts, r, sort=bool(sort)), sort, (L, r, sort))
 
 
 @needs_reference

@@ -55,7 +55,7 @@ def one_case(rng, pt, oracle, torch, case):
     dim = int(rng.choice([1, 2, 3, 3, 3, 4, 5, 7]))
     n = int(rng.choice([1, 2, 9, 100, 3000, 20000, 60000]))
     nq = int(rng.choice([1, 63, 64, 65, 1000, 5000]))
-    leaf = int(rng.choice([1, 2, 5, 10, 16, 24]))
+    leaf = int(rng.choice([1, 2, 5, 10, 16, 24, 31, 32, 33, 64, 100]))
     kind = str(rng.choice(["uniform", "clustered", "lattice", "duplicates", "line", "plane"]))
     scale = float(rng.choice([1.0, 1.0, 1e-6, 1e6, 37.5]))
     shift = float(rng.choice([0.0, 0.0, -0.5, 100.0]))
@@ -115,7 +115,7 @@ def one_topological_case(rng, pt, oracle, torch, case):
     dim = 1 if metric == "SO2" else 3
     n = int(rng.choice([2, 9, 100, 3000, 20000, 60000]))
     nq = int(rng.choice([1, 63, 64, 65, 1000, 5000]))
-    leaf = int(rng.choice([1, 2, 5, 10, 16]))
+    leaf = int(rng.choice([1, 2, 5, 10, 16, 31, 32, 33, 64, 100]))
     kind = str(rng.choice(["uniform", "clustered", "lattice", "duplicates"]))
     wrap01 = lambda a: np.ascontiguousarray(np.clip(a - np.floor(a), 0.0, 1.0).astype(DTYPE))
     pts = wrap01(make_cloud(rng, kind, n, dim))
@@ -163,7 +163,7 @@ def one_multi_case(rng, pt, oracle, torch, case):
     dim = int(rng.choice([1, 2, 3, 3]))
     n = int(rng.choice([9, 100, 3000, 20000]))
     nq = int(rng.choice([1, 2, 7, 63, 65, 1000, 5003]))
-    leaf = int(rng.choice([1, 5, 10, 16]))
+    leaf = int(rng.choice([1, 5, 10, 16, 31, 32, 33, 64, 100]))
     kind = str(rng.choice(["uniform", "clustered", "lattice", "duplicates"]))
     pts = make_cloud(rng, kind, n, dim).astype(np.float32)
     q = make_cloud(rng, kind, nq, dim).astype(np.float32)
