@@ -221,6 +221,15 @@ struct ptk_api<float> {
                                  float const* viewpoint, ptk_frame* frames, ptk_moments* moments) {
     return ptk_normals_within_self(t, radius, radii, min_neighbors, viewpoint, frames, moments);
   }
+  static int aggregate_within_self(tree const* t, float radius, float const* radii, float const* values,
+                                   std::uint32_t channels, std::uint32_t op, float* out, std::uint64_t* counts) {
+    return ptk_aggregate_within_self(t, radius, radii, values, channels, op, out, counts);
+  }
+  static int aggregate_within(tree const* t, float const* q, std::uint64_t nq, float radius, float const* radii,
+                              float const* values, std::uint32_t channels, std::uint32_t op, float* out,
+                              std::uint64_t* counts) {
+    return ptk_aggregate_within(t, q, nq, radius, radii, values, channels, op, out, counts);
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }

@@ -32,6 +32,7 @@
 #include "core.hpp"
 #include "internal/access.hpp"
 #include "internal/backend.hpp"
+#include "internal/aggregate.hpp"
 #include "internal/cluster.hpp"
 #include "internal/flat_search.hpp"
 #include "internal/flat_tree.hpp"
@@ -469,6 +470,69 @@ class kd_tree {
       std::vector<local_moments>* moments = nullptr) const {
     check_radii(radii, view().size());
     batched_normals_within_self(scalar_type(0), radii.data(), frames, min_neighbors, viewpoint, moments);
+  }
+
+  //! The sum, minimum or maximum of a per-point value over every tree point's
+  //! neighbourhood (float points).  \p values holds size() x \p channels floats,
+  //! row-major, by original point index; row i of \p out (resized to size() x
+  //! channels) folds values[j] over row i of search_radius_self (unsorted),
+  //! channel by channel in row order: sum from +0 with acc + v, max from -inf
+  //! with (v > acc) ? v : acc, min from +inf with (v < acc) ? v : acc.  With
+  //! \p include_self the fold starts at the point's own value.  \p counts, if
+  //! given, receives the row lengths.  Served by the backend
+  //! (ptk_aggregate_within_self); where it refuses (and allow_host_loop is on),
+  //! and in a build with PICO_TREE_HOST_ONLY defined, by a loop over the
+  //! per-point member with the fold of internal/aggregate.hpp: the same bytes
+  //! either way.
+  inline void aggregate_within_self(
+      scalar_type const radius,
+      scalar_type const* values,
+      size_type const channels,
+      aggregate_op const op,
+      bool const include_self,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts = nullptr) const {
+    batched_aggregate_within_self(radius, nullptr, values, channels, op, include_self, out, counts);
+  }
+
+  inline void aggregate_within_self(
+      std::vector<scalar_type> const& radii,
+      scalar_type const* values,
+      size_type const channels,
+      aggregate_op const op,
+      bool const include_self,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts = nullptr) const {
+    check_radii(radii, view().size());
+    batched_aggregate_within_self(scalar_type(0), radii.data(), values, channels, op, include_self, out, counts);
+  }
+
+  //! The same over the rows of search_radius (unsorted) of a query batch: row i
+  //! of \p out (resized to queries x channels) folds values[j] over the
+  //! neighbours of query i.  A query has no own point: this is also the form
+  //! for a subset of the tree's points.
+  template <typename QuerySpace_>
+  inline void aggregate_within(
+      QuerySpace_ const& queries,
+      scalar_type const radius,
+      scalar_type const* values,
+      size_type const channels,
+      aggregate_op const op,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts = nullptr) const {
+    batched_aggregate_within(queries, radius, nullptr, values, channels, op, out, counts);
+  }
+
+  template <typename QuerySpace_>
+  inline void aggregate_within(
+      QuerySpace_ const& queries,
+      std::vector<scalar_type> const& radii,
+      scalar_type const* values,
+      size_type const channels,
+      aggregate_op const op,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts = nullptr) const {
+    batched_aggregate_within(queries, scalar_type(0), &radii, values, channels, op, out, counts);
   }
 
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
@@ -960,6 +1024,106 @@ class kd_tree {
               reinterpret_cast<ptk_frame*>(frames.data()),
               moments != nullptr ? reinterpret_cast<ptk_moments*>(moments->data()) : nullptr),
           "ptk_normals_within_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  void check_aggregate(scalar_type const* values, size_type channels) const {
+    if (channels == 0 || channels > internal::aggregate_max_channels) {
+      throw std::invalid_argument("pico_tree: aggregate_within takes 1 .. 1024 channels");
+    }
+    if (values == nullptr) throw std::invalid_argument("pico_tree: aggregate_within needs values");
+  }
+
+  void batched_aggregate_within_self(
+      scalar_type radius,
+      scalar_type const* radii,
+      scalar_type const* values,
+      size_type channels,
+      aggregate_op op,
+      bool include_self,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(std::is_same_v<scalar_type, float>, "AGGREGATE_WITHIN_NEEDS_FLOAT_POINTS");
+    check_aggregate(values, channels);
+    size_type const n = view().size();
+    out.assign(n * channels, scalar_type(0));
+    if (counts != nullptr) counts->assign(n, 0);
+    auto const rows_loop = [&]() {
+      internal::host_rows_loop(n, [&](size_type i) {
+        std::vector<neighbor_type> row;
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, row);
+        internal::aggregate_row(
+            values, channels, op, include_self ? values + i * channels : nullptr, row, out.data() + i * channels);
+        if (counts != nullptr) (*counts)[i] = row.size();
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    std::vector<std::uint64_t> c(counts != nullptr ? n : 0);
+    try {
+      internal::ptk_check(
+          api::aggregate_within_self(
+              device(), radius, radii, values, static_cast<std::uint32_t>(channels),
+              static_cast<std::uint32_t>(op) | (include_self ? internal::aggregate_include_self : 0u), out.data(),
+              counts != nullptr ? c.data() : nullptr),
+          "ptk_aggregate_within_self");
+      if (counts != nullptr) std::copy(c.begin(), c.end(), counts->begin());
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  template <typename QuerySpace_>
+  void batched_aggregate_within(
+      QuerySpace_ const& queries,
+      scalar_type radius,
+      std::vector<scalar_type> const* radii,
+      scalar_type const* values,
+      size_type channels,
+      aggregate_op op,
+      std::vector<scalar_type>& out,
+      std::vector<size_type>* counts) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(std::is_same_v<scalar_type, float>, "AGGREGATE_WITHIN_NEEDS_FLOAT_POINTS");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    if (radii != nullptr) check_radii(*radii, q.rows());
+    check_aggregate(values, channels);
+    size_type const n = q.rows();
+    out.assign(n * channels, scalar_type(0));
+    if (counts != nullptr) counts->assign(n, 0);
+    auto const rows_loop = [&]() {
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(n, [&](size_type i) {
+        row_point x = make_row(q.data() + i * q.cols(), q.cols());
+        std::vector<neighbor_type> row;
+        search_radius(x, radii != nullptr ? (*radii)[i] : radius, row);
+        internal::aggregate_row(values, channels, op, nullptr, row, out.data() + i * channels);
+        if (counts != nullptr) (*counts)[i] = row.size();
+      });
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    std::vector<std::uint64_t> c(counts != nullptr ? n : 0);
+    try {
+      internal::ptk_check(
+          api::aggregate_within(
+              device(), q.data(), n, radius, radii != nullptr ? radii->data() : nullptr, values,
+              static_cast<std::uint32_t>(channels), static_cast<std::uint32_t>(op), out.data(),
+              counts != nullptr ? c.data() : nullptr),
+          "ptk_aggregate_within");
+      if (counts != nullptr) std::copy(c.begin(), c.end(), counts->begin());
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

@@ -542,6 +542,61 @@ int ptk_normals_within_self_device(const ptk_tree* tree, float radius, const flo
                                    const float* viewpoint /* host, 3 floats, read at the call */, ptk_frame* d_frames,
                                    ptk_moments* d_moments, void* stream);
 
+/* ---- aggregate_within: pool a caller's per-point values over radius neighbourhoods ------------------------------------
+ * The sum, minimum or maximum of `values` over every row of the self radius search (aggregate_within_self) or of a query
+ * batch (aggregate_within), accumulated inside the traversal: no rows are written.  float32 trees.  Contract (DESIGN.md
+ * section 2):
+ *   Inputs.  `values`: float32, row-major [n_points, channels], indexed by ORIGINAL point index.  `out`: float32,
+ * [n_points, channels] by original point index in the self form, [nq, channels] in the caller's query order in the query
+ * form.  `counts`: uint64 per row, may be NULL.  `op`: PTK_AGG_SUM, PTK_AGG_MIN or PTK_AGG_MAX; the self forms may OR in
+ * PTK_AGG_INCLUDE_SELF.  `radius`, or `radii` when non-NULL: the self forms take them exactly as
+ * ptk_search_count_within_self does (n_points entries by original point index), the query forms as
+ * ptk_search_radius_radii does (nq entries), with the scalar used when `radii` is NULL.
+ *   Row.  Self form: row i of ptk_search_radius_self on the same handle with the same radius or radii and sort = 0 --
+ * exact, strict <, the handle's metric, the own entry removed, the reference's traversal order.  Query form: row i of
+ * ptk_search_radius_radii with sort = 0.  Write c for its length and j_1 .. j_c for its indices in order.
+ *   Accumulation.  Per channel a, independently, in row order; every operation is one IEEE float32 operation, no
+ * contraction, no reassociation:
+ *     SUM  acc = +0,    then acc = acc + values[j_t][a]
+ *     MAX  acc = -inf,  then acc = (v > acc) ? v : acc      with v = values[j_t][a]
+ *     MIN  acc = +inf,  then acc = (v < acc) ? v : acc
+ * These formulas define the result for NaN, +-inf and signed zero: a NaN value never replaces an accumulator; of -0 and
+ * +0 the first seen stays; a NaN accumulator (INCLUDE_SELF below) stays NaN under MIN and MAX, with its bits.  Which NaN
+ * an addition gives (its sign and payload) is the processor's: a SUM is defined bit for bit where it is not NaN.
+ *   INCLUDE_SELF (self forms).  The accumulator starts at values[i][a] instead of the identity, whether or not the
+ * point's own record was in the reference's row (as normals_within_self treats the own point).  In the query forms the
+ * flag is PTK_ERR_INVALID.
+ *   Counts.  counts[i] = c, in the self form after the own entry has left; INCLUDE_SELF does not change it.  It equals
+ * count_within_self / count_within_radii with max_count = 0.
+ *   Empty rows.  Radius 0 gives an empty row; a NaN or negative `radii` entry gives an empty row in the _device forms and
+ * is PTK_ERR_INVALID in the host-buffer forms and the host loops (the message names the first such row).  An empty row
+ * gives the identity (or the own value with INCLUDE_SELF) and count 0.  Every entry of `out` is written by every call.
+ *   Arguments.  channels == 0 or channels > 1024, an unknown op, a null `values` or `out` with rows to write and
+ * out == values are PTK_ERR_INVALID.  The buffers must not overlap: channel windows re-read `values` while `out` is being
+ * written.  No alignment is required (16-byte aligned `values` and `out` with channels % 4 == 0 take 16-byte loads and
+ * stores; the bits are the same).
+ *   Handles.  float32 trees only.  The self forms are served exactly where ptk_search_count_within_self serves, the
+ * query forms where ptk_search_radius_radii does (dim <= 3, the four non-topological metrics, not the deep stack class),
+ * refused by the same checks with the same messages: PTK_ERR_UNSUPPORTED naming ptk_host_aggregate_within_self /
+ * ptk_host_aggregate_within, which serve every float32 handle, the topological metrics included.  A host-only handle:
+ * PTK_ERR_DEVICE.
+ *   State.  The radius capture is neither read nor invalidated; no side table is needed or built (the inside shortcut
+ * would change the order of the sums).  The _device forms only enqueue on `stream` and do not wait.  The self form
+ * allocates nothing; the query form takes the handle's per-stream scratch and orders the batch exactly as
+ * ptk_search_count_within_radii_device does, once per call.  A call with more channels than a lane holds accumulators
+ * (8) runs one traversal per window of 8 channels.  Two calls give identical bytes.  In the host-buffer forms the radii,
+ * queries and values go up and `out` and `counts` come down. */
+enum { PTK_AGG_SUM = 0, PTK_AGG_MIN = 1, PTK_AGG_MAX = 2, PTK_AGG_INCLUDE_SELF = 0x100 };
+int ptk_aggregate_within_self(const ptk_tree* tree, float radius, const float* radii, const float* values, uint32_t channels,
+                              uint32_t op, float* out, uint64_t* counts);
+int ptk_aggregate_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, const float* d_values,
+                                     uint32_t channels, uint32_t op, float* d_out, uint64_t* d_counts, void* stream);
+int ptk_aggregate_within(const ptk_tree* tree, const float* queries, uint64_t nq, float radius, const float* radii,
+                         const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts);
+int ptk_aggregate_within_device(const ptk_tree* tree, const float* d_queries, uint64_t nq, float radius, const float* d_radii,
+                                const float* d_values, uint32_t channels, uint32_t op, float* d_out, uint64_t* d_counts,
+                                void* stream);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -604,6 +659,14 @@ int ptk_host_cluster_within_self(const ptk_tree* tree, const float* points, floa
  * deep stack class included; dim != 3 or a topological metric is PTK_ERR_INVALID) */
 int ptk_host_normals_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
                                  uint64_t min_neighbors, const float* viewpoint, ptk_frame* frames, ptk_moments* moments);
+/* (ptk_aggregate_within_self / ptk_aggregate_within as the contract reads: the rows of ptk_host_search_radius_self /
+ * ptk_host_search_radius_radii, unsorted, folded with the formulas verbatim; every float32 handle, the deep stack class
+ * and the topological metrics included) */
+int ptk_host_aggregate_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
+                                   const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts);
+int ptk_host_aggregate_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
+                              const float* radii, const float* values, uint32_t channels, uint32_t op, float* out,
+                              uint64_t* counts);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 

@@ -42,6 +42,9 @@ NEIGHBOR = np.dtype([("index", "<i4"), ("distance", "<f4")])
 #: ptk_frame / ptk_moments (ptk.h): the records of KdTree.normals_within_self
 FRAME = np.dtype([("normal", "<f4", (3,)), ("curvature", "<f4"), ("eigenvalues", "<f4", (3,)), ("count", "<u4")])
 MOMENTS = np.dtype([("sum", "<f4", (3,)), ("count", "<u4"), ("outer", "<f4", (6,)), ("pad_", "<u4", (2,))])
+#: PTK_AGG_* (ptk.h): the ops of KdTree.aggregate_within_self / aggregate_within
+PTK_AGG_SUM, PTK_AGG_MIN, PTK_AGG_MAX, PTK_AGG_INCLUDE_SELF = 0, 1, 2, 0x100
+_AGGREGATE_OPS = {"sum": PTK_AGG_SUM, "min": PTK_AGG_MIN, "max": PTK_AGG_MAX}
 #: The same record of a tree over float64 points: ``neighbor<int, double>`` is 16 bytes with the
 #: distance at offset 8, which is what the reference binding's PYBIND11_NUMPY_DTYPE yields for it
 #: (_pyco_tree/def_core.hpp:17-18).
@@ -106,6 +109,13 @@ _SIGNATURES = {
     "ptk_normals_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
     "ptk_normals_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p,
                                                c_void_p]),
+    "ptk_aggregate_within_self": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
+    "ptk_aggregate_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "ptk_aggregate_within": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p,
+                                     c_void_p]),
+    "ptk_aggregate_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32, c_uint32,
+                                            c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -140,6 +150,10 @@ _SIGNATURES = {
     "ptk_host_cluster_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_host_normals_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p,
                                              c_void_p]),
+    "ptk_host_aggregate_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p,
+                                               c_void_p]),
+    "ptk_host_aggregate_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32,
+                                          c_uint32, c_void_p, c_void_p]),
     "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -1263,6 +1277,142 @@ class KdTree:
                      lambda lib: lib.ptk_host_normals_within_self(self._h, self._pts.ctypes.data, r, rp, min_neighbors, vp,
                                                                   frames.ctypes.data, mp))
         return (frames, mom) if moments else frames
+
+    def _aggregate_op(self, op, include_self: bool = False) -> int:
+        try:
+            code = _AGGREGATE_OPS[op]
+        except (KeyError, TypeError):
+            raise ValueError(f"op must be one of {sorted(_AGGREGATE_OPS)}, not {op!r}") from None
+        return code | (PTK_AGG_INCLUDE_SELF if include_self else 0)
+
+    def _aggregate_values(self, values, device):
+        """(values as a contiguous float32 [npts, channels] array or CUDA tensor, channels, was it 1-D).  ``device``: None
+        for a host call, else the torch device the tensor must live on."""
+        n = self._npts
+        if device is not None:
+            import torch
+            if not (_is_torch(values) and values.is_cuda):
+                raise ValueError("values must be a CUDA tensor for a device call")
+            if values.device != device:
+                raise ValueError(f"values must be on {device}, not on {values.device}")
+            if values.dtype != torch.float32:
+                raise ValueError(f"values must be a float32 tensor, not {values.dtype}")
+            if not values.is_contiguous():
+                raise ValueError("values must be a contiguous tensor")
+            shape = tuple(values.shape)
+        else:
+            if _is_torch(values):
+                if values.is_cuda:
+                    raise ValueError("values: a host call takes a host array, not a CUDA tensor")
+                values = values.numpy()
+            values = np.asarray(values)
+            if values.dtype != np.float32:
+                raise ValueError(f"values must be a float32 array, not {values.dtype}")
+            values = np.ascontiguousarray(values)
+            shape = values.shape
+        if len(shape) not in (1, 2) or shape[0] != n:
+            raise ValueError(f"values must have shape ({n},) or ({n}, channels), not {tuple(shape)}")
+        flat = len(shape) == 1
+        channels = 1 if flat else int(shape[1])
+        if not 1 <= channels <= 1024:
+            raise ValueError(f"values must hold 1 .. 1024 channels, not {channels}")
+        return values, channels, flat
+
+    def aggregate_within_self(self, radius, values, op: str = "sum", include_self: bool = False, counts: bool = False,
+                              device: bool = False):
+        """``aggregate_within_self(radius, values, op="sum", include_self=False, counts=False, device=False)`` -- the sum,
+        minimum or maximum of a per-point value over every tree point's neighbourhood.
+
+        The neighbourhood of point i is :meth:`search_radius_self`'s row i (unsorted: the other points closer than
+        ``radius``); ``values`` is ``(npts,)`` or ``(npts, channels)`` float32 by original point index, and row i of the
+        result folds ``values[j]`` over the row, channel by channel, in row order (``ptk_aggregate_within_self``: the
+        exact float32 formulas are in ``ptk.h``).  No rows are written.  ``op`` is ``"sum"``, ``"min"`` or ``"max"``; an
+        empty row gives 0, +inf or -inf.  With ``include_self`` the fold starts at the point's own value instead.
+        ``radius`` is a scalar or an array of ``npts`` radii by original point index.  A 1-D ``values`` gives a 1-D
+        result.  With ``counts=True`` returns ``(out, counts)``, ``counts`` the ``int64`` row lengths (mean = sum /
+        count).  With ``device=True`` ``values`` is a contiguous CUDA tensor on the tree's device and the results are
+        CUDA tensors, enqueued on the current torch stream.  float32 trees; served where :meth:`count_within_self` is,
+        the rest is refused (``allow_host_loop`` serves every float32 tree)."""
+        self._float32_only("aggregate_within_self")
+        code = self._aggregate_op(op, include_self)
+        n = self._npts
+        lib = _load()
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            values, channels, flat = self._aggregate_values(values, dev)
+            r, radii = self._self_radii(radius, True)
+            out = torch.empty((n, channels), dtype=torch.float32, device=dev)
+            cnt = torch.empty((n,), dtype=torch.int64, device=dev) if counts else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.ptk_aggregate_within_self_device(self._h, r, radii.data_ptr() if radii is not None else None,
+                                                        values.data_ptr(), channels, code, out.data_ptr(),
+                                                        cnt.data_ptr() if counts else None, stream))
+        else:
+            values, channels, flat = self._aggregate_values(values, None)
+            r, radii = self._self_radii(radius, False)
+            out = np.zeros((n, channels), dtype=np.float32)
+            cnt = np.zeros((n,), dtype=np.int64) if counts else None
+            rp = radii.ctypes.data if radii is not None else None
+            cp = cnt.ctypes.data if counts else None
+            self._served(lib.ptk_aggregate_within_self(self._h, r, rp, values.ctypes.data, channels, code, out.ctypes.data, cp),
+                         lambda lib: lib.ptk_host_aggregate_within_self(self._h, self._pts.ctypes.data, r, rp,
+                                                                        values.ctypes.data, channels, code,
+                                                                        out.ctypes.data, cp))
+        if flat:
+            out = out.reshape(n)
+        return (out, cnt) if counts else out
+
+    def aggregate_within(self, pts, radius, values, op: str = "sum", counts: bool = False):
+        """``aggregate_within(pts, radius, values, op="sum", counts=False)`` -- the sum, minimum or maximum of a per-point
+        value over the neighbourhood of each query.
+
+        Row i of the result folds ``values[j]`` over :meth:`search_radius`'s unsorted row i of ``pts`` (``e = 1``), as
+        :meth:`aggregate_within_self` does over the tree's own rows -- a query has no own point, so this is also the
+        form for a subset of the tree's points (``ptk_aggregate_within``).  ``radius`` is a scalar or one radius per
+        query.  Host ``pts`` take a float32 numpy ``values`` and return numpy arrays; a contiguous CUDA ``pts`` tensor
+        takes a CUDA ``values`` tensor on the same device, is enqueued on the current torch stream and returns tensors.
+        float32 trees; served where :meth:`search_radius` with per-row radii is, the rest is refused
+        (``allow_host_loop`` serves every float32 tree)."""
+        self._float32_only("aggregate_within")
+        code = self._aggregate_op(op)
+        radii = None if _is_scalar_radius(radius) else radius
+        r = self._real(radius) if radii is None else self._real(0)
+        lib = _load()
+        if _is_torch(pts):
+            import torch
+            if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != self._sdim:
+                raise ValueError("queries must be a float32 (nq, sdim) tensor")
+            if not pts.is_cuda or not pts.is_contiguous():
+                raise ValueError("queries must be a contiguous CUDA tensor")
+            nq = pts.shape[0]
+            values, channels, flat = self._aggregate_values(values, pts.device)
+            if radii is not None:
+                radii = self._device_radii(radii, pts, nq)
+            out = torch.empty((nq, channels), dtype=torch.float32, device=pts.device)
+            cnt = torch.empty((nq,), dtype=torch.int64, device=pts.device) if counts else None
+            stream = torch.cuda.current_stream(pts.device).cuda_stream
+            _check(lib.ptk_aggregate_within_device(self._h, pts.data_ptr(), nq, r,
+                                                   radii.data_ptr() if radii is not None else None, values.data_ptr(),
+                                                   channels, code, out.data_ptr(), cnt.data_ptr() if counts else None,
+                                                   stream))
+        else:
+            q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
+            nq = q.shape[0]
+            values, channels, flat = self._aggregate_values(values, None)
+            if radii is not None:
+                radii = self._host_radii(radii, nq)
+            out = np.zeros((nq, channels), dtype=np.float32)
+            cnt = np.zeros((nq,), dtype=np.int64) if counts else None
+            rp = radii.ctypes.data if radii is not None else None
+            cp = cnt.ctypes.data if counts else None
+            self._served(lib.ptk_aggregate_within(self._h, q.ctypes.data, nq, r, rp, values.ctypes.data, channels, code,
+                                                  out.ctypes.data, cp),
+                         lambda lib: lib.ptk_host_aggregate_within(self._h, self._pts.ctypes.data, q.ctypes.data, nq, r, rp,
+                                                                   values.ctypes.data, channels, code, out.ctypes.data, cp))
+        if flat:
+            out = out.reshape(nq)
+        return (out, cnt) if counts else out
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

@@ -2614,6 +2614,97 @@ int ptk_normals_within_self(const ptk_tree* t, float radius, const float* radii,
   return PTK_OK;
 }
 
+// ---- aggregate_within_self / aggregate_within (ptk.h; the kernels: ptk_kernels_aggregate.hpp) ---------------
+
+// Enqueues aggregate_self_kernel over ranges of leaf positions, one launch per channel window: no scratch, nothing
+// allocated, nothing waited for, no side table.  The handle's radius capture is neither read nor invalidated.
+int ptk_aggregate_within_self_device(const ptk_tree* t, float radius, const float* d_radii, const float* d_values,
+                                     uint32_t channels, uint32_t op, float* d_out, uint64_t* d_counts, void* stream) {
+  const int rc = check_aggregate_self(t, radius, d_radii, /*host_values=*/false, d_values, channels, op, d_out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  return in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+    return ptkf::aggregate_self(t, first, n, radius, d_radii, d_values, channels, op, d_out, d_counts, s);
+  });
+}
+
+// The query form: the batch order of ptk_search_count_within_radii_device in a scratch block of the stream's own,
+// computed once for every channel window.  It never goes through radius_pass_device (the radius capture stays).
+int ptk_aggregate_within_device(const ptk_tree* t, const float* d_q, uint64_t nq, float radius, const float* d_radii,
+                                const float* d_values, uint32_t channels, uint32_t op, float* d_out, uint64_t* d_counts,
+                                void* stream) {
+  int rc = check_aggregate_within(t, d_q, nq, radius, d_radii, /*host_values=*/false, d_values, channels, op, d_out);
+  if (rc != PTK_OK || nq == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  Scratch scratch(t, s, /*per_stream=*/true);
+  uint32_t* perm = nullptr;
+  rc = order_batch(t, d_q, nq, s, scratch, 0, &perm, ptk::kCellsDenseFirst);
+  if (rc != PTK_OK) return rc;
+  return ptkf::aggregate_within(t, d_q, perm, nq, radius, d_radii, d_values, channels, op, d_out, d_counts, s);
+}
+
+// The host-buffer forms: the values, then the queries and the radii go up in the handle's input block (each part on a
+// 16-byte boundary), `out` and the counts come down from its output block.  q null: the self form.
+static int aggregate_round_trip(const ptk_tree* t, const float* q, uint64_t nq, float radius, const float* radii,
+                                const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts) {
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const bool self_form = q == nullptr;
+  const uint64_t rows = self_form ? t->n_points : nq;
+  const auto pad16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+  const size_t value_bytes = (size_t)t->n_points * channels * sizeof(float);
+  const size_t q_bytes = self_form ? 0 : (size_t)nq * t->dim * sizeof(float);
+  const size_t radii_bytes = radii != nullptr ? (size_t)rows * sizeof(float) : 0;
+  const size_t out_bytes = (size_t)rows * channels * sizeof(float);
+  const size_t count_bytes = counts != nullptr ? (size_t)rows * sizeof(uint64_t) : 0;
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  hipStream_t s = io.search[0];
+  int rc = grow_device_block(&io.d_in, &io.in_capacity, pad16(value_bytes) + pad16(q_bytes) + radii_bytes);
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, pad16(out_bytes) + count_bytes);
+  if (rc != PTK_OK) return rc;
+  char* d_values = io.d_in;
+  char* d_q = d_values + pad16(value_bytes);
+  char* d_radii = d_q + pad16(q_bytes);
+  PTK_HIP(hipMemcpyAsync(d_values, values, value_bytes, hipMemcpyHostToDevice, s));
+  if (!self_form) PTK_HIP(hipMemcpyAsync(d_q, q, q_bytes, hipMemcpyHostToDevice, s));
+  if (radii != nullptr) PTK_HIP(hipMemcpyAsync(d_radii, radii, radii_bytes, hipMemcpyHostToDevice, s));
+  const float* dr = radii != nullptr ? reinterpret_cast<const float*>(d_radii) : nullptr;
+  auto* d_out = reinterpret_cast<float*>(io.d_out);
+  auto* d_counts = counts != nullptr ? reinterpret_cast<uint64_t*>(io.d_out + pad16(out_bytes)) : nullptr;
+  rc = self_form ? ptk_aggregate_within_self_device(t, radius, dr, reinterpret_cast<const float*>(d_values), channels, op,
+                                                    d_out, d_counts, s)
+                 : ptk_aggregate_within_device(t, reinterpret_cast<const float*>(d_q), nq, radius, dr,
+                                               reinterpret_cast<const float*>(d_values), channels, op, d_out, d_counts, s);
+  if (rc != PTK_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  PTK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+  if (counts != nullptr) PTK_HIP(hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, s));
+  PTK_HIP(hipStreamSynchronize(s));
+  return PTK_OK;
+}
+
+int ptk_aggregate_within_self(const ptk_tree* t, float radius, const float* radii, const float* values, uint32_t channels,
+                              uint32_t op, float* out, uint64_t* counts) {
+  const int rc = check_aggregate_self(t, radius, radii, /*host_values=*/true, values, channels, op, out);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  return aggregate_round_trip(t, nullptr, 0, radius, radii, values, channels, op, out, counts);
+}
+
+int ptk_aggregate_within(const ptk_tree* t, const float* q, uint64_t nq, float radius, const float* radii,
+                         const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts) {
+  const int rc = check_aggregate_within(t, q, nq, radius, radii, /*host_values=*/true, values, channels, op, out);
+  if (rc != PTK_OK || nq == 0) return rc;
+  return aggregate_round_trip(t, q, nq, radius, radii, values, channels, op, out, counts);
+}
+
 }  // extern "C"
 
 namespace {

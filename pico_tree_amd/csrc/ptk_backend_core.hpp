@@ -766,6 +766,52 @@ inline int check_normals_self(const ptk_tree* t, double radius, const float* rad
                            "ptk_host_normals_within_self");
 }
 
+// aggregate_within_self / aggregate_within (ptk.h): the arguments of their own, looked at before the handle (a host-only
+// handle refuses a bad argument as a bad argument).  `rows`: the rows the call would write.
+inline int check_aggregate_args(const void* values, uint32_t channels, uint32_t op, bool self_form, const void* out,
+                                uint64_t rows) {
+  if (channels == 0 || channels > 1024u)
+    return fail(PTK_ERR_INVALID, "aggregate_within: channels must be 1 .. 1024, not %u", channels);
+  const uint32_t kind = op & ~(uint32_t)PTK_AGG_INCLUDE_SELF;
+  if (kind != PTK_AGG_SUM && kind != PTK_AGG_MIN && kind != PTK_AGG_MAX)
+    return fail(PTK_ERR_INVALID, "aggregate_within: unknown op %u", op);
+  if (!self_form && (op & PTK_AGG_INCLUDE_SELF) != 0)
+    return fail(PTK_ERR_INVALID, "aggregate_within: PTK_AGG_INCLUDE_SELF belongs to the self forms (a query row has no own point)");
+  if (rows > 0 && (values == nullptr || out == nullptr)) return fail(PTK_ERR_INVALID, "null values or output buffer");
+  if (rows > 0 && out == values) return fail(PTK_ERR_INVALID, "aggregate_within: out and values must not overlap");
+  return PTK_OK;
+}
+// The self forms: then the checks of count_within_self, with its messages.
+inline int check_aggregate_self(const ptk_tree* t, double radius, const float* radii, bool host_values, const void* values,
+                                uint32_t channels, uint32_t op, const void* out) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  const int rc = check_aggregate_args(values, channels, op, /*self_form=*/true, out, t->n_points);
+  if (rc != PTK_OK) return rc;
+  return check_radius_self(t, radius, radii, host_values, out, "aggregate_within_self", "ptk_host_aggregate_within_self");
+}
+// The query forms: then the checks of search_radius_radii (`radii` null: the scalar `radius`), whose refusal of a handle
+// is passed on with the host loop that serves it.
+inline int check_aggregate_within(const ptk_tree* t, const void* q, uint64_t nq, double radius, const float* radii,
+                                  bool host_values, const void* values, uint32_t channels, uint32_t op, const void* out) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  int rc = check_aggregate_args(values, channels, op, /*self_form=*/false, out, nq);
+  if (rc != PTK_OK) return rc;
+  rc = check_search(t, q, nq);
+  if (rc != PTK_OK || nq == 0) return rc;
+  if (radii == nullptr) {
+    rc = check_radius(radius);
+    if (rc != PTK_OK) return rc;
+  }
+  // (a scalar call has no array to scan: the check is shown the queries in its place, and only that they are there)
+  rc = check_radius_radii(t, q, nq, radii != nullptr ? radii : static_cast<const float*>(q), out,
+                          host_values && radii != nullptr);
+  if (rc == PTK_ERR_UNSUPPORTED) {
+    const std::string why = ptk_last_error();
+    return fail(PTK_ERR_UNSUPPORTED, "aggregate_within: %s (ptk_host_aggregate_within)", why.c_str());
+  }
+  return rc;
+}
+
 // cluster_within_self (ptk.h): n_clusters of the host forms -- the labels that name their own entry.
 inline uint64_t count_cluster_roots(const int32_t* labels, uint64_t n) {
   uint64_t roots = 0;

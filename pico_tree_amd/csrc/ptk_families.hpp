@@ -113,6 +113,12 @@ int count_within_radii(const ptk_tree* t, const float* d_q, const uint32_t* perm
 // search_radius_radii (ptk.h): the rows behind count_within_radii(max_count = 0) and a scan of its counts
 int radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, const float* d_radii,
                       const uint64_t* d_offsets, ptk::Neighbor* d_out, hipStream_t s);
+// aggregate_within (ptk_kernels_aggregate.hpp): out[qi][0 .. channels) and counts[qi] (may be null) of
+// the rows of radius_radii_fill at e = 1; d_radii null: every row gets `radius`.  `flags`: a PTK_AGG_* op.  One launch
+// per channel window.
+int aggregate_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius,
+                     const float* d_radii, const float* d_values, uint32_t channels, uint32_t flags, float* d_out,
+                     uint64_t* d_counts, hipStream_t s);
 int clamp_counts(uint64_t* d_counts, uint64_t n, uint64_t max_count, hipStream_t s);
 // ... and of float64 trees with dim <= 3 (ptk_kernels_count64.hpp): kCountBox64Bytes per branch
 constexpr size_t kCountBox64Bytes = 64;
@@ -167,6 +173,11 @@ int cluster_elementwise(int pass, uint64_t n, bool compress, int32_t* d_labels, 
 // viewpoint, else 3 host floats.
 int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, uint64_t min_neighbors,
                 const float* view, ptk_frame* d_frames, ptk_moments* d_moments, hipStream_t s);
+// aggregate_within_self (ptk_kernels_aggregate.hpp): out[index][0 .. channels) and counts[index] (may
+// be null) of leaf positions [first, first + n) of a float32 handle that check_radius_self serves.  `flags`: a PTK_AGG_*
+// op, | PTK_AGG_INCLUDE_SELF.  One launch per channel window.
+int aggregate_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, const float* d_values,
+                   uint32_t channels, uint32_t flags, float* d_out, uint64_t* d_counts, hipStream_t s);
 void warm_self();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.

@@ -1,8 +1,10 @@
 // ptk_family_count.hip -- count_within of 3-D float32 trees (ptk_kernels_count.hpp): the per-branch side table and
-// the count kernel with its two shortcuts; the clamp of the other families' counts.
+// the count kernel with its two shortcuts; the clamp of the other families' counts; aggregate_within
+// (ptk_kernels_aggregate.hpp, K21): the sum / min / max of a caller's values over the rows of the per-row fill pass.
 // One of the translation units of libptk.so (ptk_backend_core.hpp).
 
 #include "ptk_families.hpp"
+#include "ptk_kernels_aggregate.hpp"
 #include "ptk_kernels_count.hpp"
 #include "ptk_kernels_count64.hpp"
 
@@ -46,6 +48,27 @@ int launch_radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t
   Timer timer(t, s);
   hipLaunchKernelGGL((ptk::radius_radii_fill_kernel<S, OVF, 64, LEAFB, M>), dim3(blocks), dim3(64), (size_t)S * 64 * 8, s,
                      t->dev, d_q, t->dim, perm, nq, d_radii, d_offsets, d_out);
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, nq);
+  return PTK_OK;
+}
+
+// aggregate_within: the launch geometry of launch_radius_radii_fill, one launch per channel window.
+template <int S, int OVF, int LEAFB, class M>
+int launch_aggregate_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius,
+                            const float* d_radii, const float* d_values, uint32_t channels, uint32_t flags, float* d_out,
+                            uint64_t* d_counts, hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((nq + 63) / 64);
+  Timer timer(t, s);
+  ptkd::with_bool(d_radii != nullptr, [&](auto per_row) {
+    constexpr bool PER_ROW = decltype(per_row)::value;
+    return ptk::aggregate_windows(d_values, d_out, channels, [&](auto W, auto VEC, uint32_t c0, uint32_t w) {
+      hipLaunchKernelGGL((ptk::aggregate_within_kernel<W, VEC, S, OVF, 64, LEAFB, PER_ROW, M>), dim3(blocks), dim3(64),
+                         (size_t)S * 64 * 8, s, t->dev, d_q, t->dim, perm, nq, radius, d_radii, d_values, channels, c0, w,
+                         flags, d_out, d_counts);
+      return PTK_OK;
+    });
+  });
   PTK_HIP(hipGetLastError());
   timer.stop(0, nq);
   return PTK_OK;
@@ -104,6 +127,15 @@ int radius_radii_fill(const ptk_tree* t, const float* d_q, const uint32_t* perm,
   return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
     return launch_radius_radii_fill<16, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, d_radii, d_offsets,
         d_out, s);
+  });
+}
+
+int aggregate_within(const ptk_tree* t, const float* d_q, const uint32_t* perm, uint64_t nq, float radius,
+                     const float* d_radii, const float* d_values, uint32_t channels, uint32_t flags, float* d_out,
+                     uint64_t* d_counts, hipStream_t s) {
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_aggregate_within<16, ovf, kGenLeafB, ptkd::type_of<decltype(m)>>(t, d_q, perm, nq, radius, d_radii,
+        d_values, channels, flags, d_out, d_counts, s);
   });
 }
 

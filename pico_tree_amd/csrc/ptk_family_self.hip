@@ -4,10 +4,12 @@
 // float64; search_radius_self / count_within_self (ptk_kernels_selfr.hpp, K18): the count and fill kernels over the tree's
 // own records, float32 and float64, each written once over its radius source; cluster_within_self
 // (ptk_kernels_cluster.hpp, K19): the mark, link and border kernels over the same records and the elementwise passes;
-// normals_within_self (ptk_kernels_frames.hpp, K20): the moments and frames kernel over the same records.
+// normals_within_self (ptk_kernels_frames.hpp, K20): the moments and frames kernel over the same records;
+// aggregate_within_self (ptk_kernels_aggregate.hpp, K21): the sum / min / max of a caller's values over the same rows.
 // One of the translation units of libptk.so (ptk_backend_core.hpp).
 
 #include "ptk_families.hpp"
+#include "ptk_kernels_aggregate.hpp"
 #include "ptk_kernels_f64.hpp"
 #include "ptk_kernels_cluster.hpp"
 #include "ptk_kernels_frames.hpp"
@@ -163,6 +165,27 @@ int launch_frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radi
   return PTK_OK;
 }
 
+// aggregate_within_self: the launch geometry of the self fill kernel, one launch per channel window.
+template <int S, int OVF, class M>
+int launch_aggregate_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii,
+                          const float* d_values, uint32_t channels, uint32_t flags, float* d_out, uint64_t* d_counts,
+                          hipStream_t s) {
+  const uint32_t blocks = (uint32_t)((n + 63) / 64);
+  Timer timer(t, s);
+  ptkd::with_bool(d_radii != nullptr, [&](auto per_row) {
+    constexpr bool PER_ROW = decltype(per_row)::value;
+    return ptk::aggregate_windows(d_values, d_out, channels, [&](auto W, auto VEC, uint32_t c0, uint32_t w) {
+      hipLaunchKernelGGL((ptk::aggregate_self_kernel<W, VEC, S, OVF, 64, kGenLeafB, PER_ROW, M>), dim3(blocks), dim3(64),
+                         (size_t)S * 64 * 8, s, t->dev, t->dim, first, n, radius, d_radii, d_values, channels, c0, w, flags,
+                         d_out, d_counts);
+      return PTK_OK;
+    });
+  });
+  PTK_HIP(hipGetLastError());
+  timer.stop(0, n);
+  return PTK_OK;
+}
+
 static __global__ void warm_self_kernel() {}
 
 }  // namespace
@@ -269,6 +292,15 @@ int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, con
   return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
     return launch_frames_self<16, ovf, ptkd::type_of<decltype(m)>>(t, first, n, radius, d_radii, min_neighbors, view, frames,
                                                                   moments, s);
+  });
+}
+
+int aggregate_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, const float* d_values,
+                   uint32_t channels, uint32_t flags, float* d_out, uint64_t* d_counts, hipStream_t s) {
+  if (t->dim > 3) return fail(PTK_ERR_INVALID, "aggregate_self: not a call of the self kernels");
+  return with_metric_ovf(t, 16, [&](auto m, auto ovf) {
+    return launch_aggregate_self<16, ovf, ptkd::type_of<decltype(m)>>(t, first, n, radius, d_radii, d_values, channels, flags,
+                                                                     d_out, d_counts, s);
   });
 }
 

@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "pico_tree/internal/aggregate.hpp"
 #include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
 #include "pico_tree/internal/local_frame.hpp"
@@ -516,6 +517,71 @@ int ptk_host_normals_within_self(const ptk_tree* t, const float* points, float r
         const internal::moments3 m = sums.record();
         std::memcpy(moments + i, &m, sizeof m);
       }
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// aggregate_within_self (ptk.h) as the contract reads: the row of the self loop above for each point, unsorted, folded with
+// the formulas of pico_tree/internal/aggregate.hpp.  Every float32 handle, the deep stack class and the topological
+// metrics included.
+int ptk_host_aggregate_within_self(const ptk_tree* t, const float* points, float radius, const float* radii,
+                                   const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  int rc = check_aggregate_args(values, channels, op, /*self_form=*/true, out, t->n_points);
+  if (rc == PTK_OK) rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc != PTK_OK) return rc;
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    const auto kind = static_cast<pico_tree::aggregate_op>(op & ~(uint32_t)PTK_AGG_INCLUDE_SELF);
+    const bool include_self = (op & PTK_AGG_INCLUDE_SELF) != 0;
+    rows_loop(t->n_points, [&](uint64_t i) {
+      std::vector<neighbor_t> row;
+      radius_self_row(t, flat, view, points, i, radii != nullptr ? radii[i] : radius, 0, row);
+      internal::aggregate_row(values, channels, kind, include_self ? values + i * channels : nullptr, row, out + i * channels);
+      if (counts != nullptr) counts[i] = row.size();
+    });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// aggregate_within (ptk.h): the same over the rows of ptk_host_search_radius_radii (e = 1, unsorted); `radii` null: every
+// row gets `radius`.
+int ptk_host_aggregate_within(const ptk_tree* t, const float* points, const float* q, uint64_t nq, float radius,
+                              const float* radii, const float* values, uint32_t channels, uint32_t op, float* out,
+                              uint64_t* counts) {
+  if (t == nullptr || points == nullptr || (nq > 0 && q == nullptr)) return fail(PTK_ERR_INVALID, "null argument");
+  int rc = check_aggregate_args(values, channels, op, /*self_form=*/false, out, nq);
+  if (rc != PTK_OK || nq == 0) return rc;
+  rc = radii != nullptr ? check_radii(radii, nq, /*host_values=*/true) : check_radius(radius);
+  if (rc != PTK_OK) return rc;
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    const auto kind = static_cast<pico_tree::aggregate_op>(op);
+    rows_loop(nq, [&](uint64_t i) {
+      std::vector<neighbor_t> row;
+      internal::radius_visitor<neighbor_t> v(radii != nullptr ? radii[i] : radius, row);
+      search_one(t, flat, view, q + i * t->dim, v);
+      internal::aggregate_row(values, channels, kind, nullptr, row, out + i * channels);
+      if (counts != nullptr) counts[i] = row.size();
     });
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
