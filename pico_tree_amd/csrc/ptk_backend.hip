@@ -13,6 +13,7 @@
 #include "ptk_sort.hpp"
 #include "ptk_forest.hpp"
 #include "ptk_rows_out.hpp"
+#include "ptk_io_parts.hpp"
 
 namespace {
 
@@ -1926,35 +1927,31 @@ int ptk_search_knn_within_radii_device(const ptk_tree* t, const float* d_q, uint
 
 namespace {
 
-// The host-buffer form of a search whose rows have one size: the batch goes up, is searched on one stream of the
-// handle and comes down, under the handle's I/O lock.  `search(d_q, d_out, stream)` is the _device form.
-// The _radii forms pass `radii` (nq host values): they go up behind the queries in the same input block, and *d_radii is
-// where `search` finds them.
+// The host-buffer form of every call whose rows have one size, written once: under the handle's I/O lock the input parts
+// go up into the handle's input block, `search(d_in, d_out, stream)` -- the _device form, which finds its device pointers
+// with in.at<T>(d_in, i) and out.at<T>(d_out, i) -- runs on one stream of the handle, and the output parts come down
+// from its output block.  An absent part (ptk_io_parts.hpp) is neither copied nor given room.
 template <class Search>
-int host_round_trip(const ptk_tree* t, const float* q, uint64_t nq, void* out, size_t out_bytes, Search&& search,
-                    const float* radii = nullptr, const float** d_radii = nullptr) {
+int host_form(const ptk_tree* t, const ptkio::Parts& in, const ptkio::Parts& out, Search&& search) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t in_bytes = (size_t)nq * t->dim * sizeof(float);
-  const size_t radii_bytes = radii != nullptr ? (size_t)nq * sizeof(float) : 0;
   HostIo& io = t->io;
   std::lock_guard<std::mutex> lock(io.mutex);
   if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int rc = grow_device_block(&io.d_in, &io.in_capacity, in_bytes + radii_bytes);
-  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
+  hipStream_t s = io.search[0];
+  int rc = grow_device_block(&io.d_in, &io.in_capacity, in.total());
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, out.total());
   if (rc != PTK_OK) return rc;
-  PTK_HIP(hipMemcpyAsync(io.d_in, q, in_bytes, hipMemcpyHostToDevice, io.search[0]));
-  if (radii != nullptr) {
-    PTK_HIP(hipMemcpyAsync(io.d_in + in_bytes, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
-    *d_radii = reinterpret_cast<const float*>(io.d_in + in_bytes);
-  }
-  rc = search(reinterpret_cast<const float*>(io.d_in), io.d_out, io.search[0]);
+  for (int i = 0; i < in.size(); ++i)
+    if (in.present(i)) PTK_HIP(hipMemcpyAsync(io.d_in + in.offset(i), in.source(i), in.bytes(i), hipMemcpyHostToDevice, s));
+  rc = search(io.d_in, io.d_out, s);
   if (rc != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
+    (void)hipStreamSynchronize(s);
     return rc;
   }
-  PTK_HIP(hipMemcpyAsync(out, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
+  for (int i = 0; i < out.size(); ++i)
+    if (out.present(i)) PTK_HIP(hipMemcpyAsync(out.destination(i), io.d_out + out.offset(i), out.bytes(i), hipMemcpyDeviceToHost, s));
+  PTK_HIP(hipStreamSynchronize(s));
   return PTK_OK;
 }
 
@@ -1965,8 +1962,10 @@ extern "C" {
 int ptk_search_knn_within(const ptk_tree* t, const float* q, uint64_t nq, uint32_t k, float radius, ptk_neighbor* out) {
   const int rc = check_knn_within(t, q, nq, k, radius, out);
   if (rc != PTK_OK || nq == 0) return rc;
-  return host_round_trip(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor), [&](const float* d_q, char* d_out, hipStream_t s) {
-    return ptk_search_knn_within_device(t, d_q, nq, k, radius, reinterpret_cast<ptk_neighbor*>(d_out), s);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(float))};
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)nq * k * sizeof(ptk_neighbor))};
+  return host_form(t, in, rows, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_search_knn_within_device(t, in.at<float>(d_in, 0), nq, k, radius, rows.at<ptk_neighbor>(d_out, 0), s);
   });
 }
 
@@ -1974,13 +1973,12 @@ int ptk_search_knn_within_radii(const ptk_tree* t, const float* q, uint64_t nq, 
                                 ptk_neighbor* out) {
   const int rc = check_knn_within_radii(t, q, nq, k, radii, out, /*host_values=*/true);
   if (rc != PTK_OK || nq == 0) return rc;
-  const float* d_radii = nullptr;
-  return host_round_trip(
-      t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor),
-      [&](const float* d_q, char* d_out, hipStream_t s) {
-        return ptk_search_knn_within_radii_device(t, d_q, nq, k, d_radii, reinterpret_cast<ptk_neighbor*>(d_out), s);
-      },
-      radii, &d_radii);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(float)), ptkio::in_part(radii, (size_t)nq * sizeof(float))};
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)nq * k * sizeof(ptk_neighbor))};
+  return host_form(t, in, rows, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_search_knn_within_radii_device(t, in.at<float>(d_in, 0), nq, k, in.at<float>(d_in, 1),
+                                              rows.at<ptk_neighbor>(d_out, 0), s);
+  });
 }
 
 // ---- each tree point's k nearest other points -------------------------------
@@ -2023,22 +2021,10 @@ int ptk_search_knn_self_device(const ptk_tree* t, uint32_t k, ptk_neighbor* d_ou
 int ptk_search_knn_self(const ptk_tree* t, uint32_t k, ptk_neighbor* out) {
   const int rc = check_knn_self(t, k, out);
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t out_bytes = (size_t)t->n_points * k * sizeof(ptk_neighbor);
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
-  if (src != PTK_OK) return src;
-  src = ptk_search_knn_self_device(t, k, reinterpret_cast<ptk_neighbor*>(io.d_out), io.search[0]);
-  if (src != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
-    return src;
-  }
-  PTK_HIP(hipMemcpyAsync(out, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
-  return PTK_OK;
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)t->n_points * k * sizeof(ptk_neighbor))};
+  return host_form(t, ptkio::Parts{}, rows, [&](char*, char* d_out, hipStream_t s) {
+    return ptk_search_knn_self_device(t, k, rows.at<ptk_neighbor>(d_out, 0), s);
+  });
 }
 
 int ptk_debug_self_route(const ptk_tree* t, uint32_t k, int* route) {
@@ -2108,8 +2094,10 @@ int ptk_search_count_within(const ptk_tree* t, const float* q, uint64_t nq, floa
                             uint64_t* counts) {
   const int rc = check_count_within(t, q, nq, radius, counts);
   if (rc != PTK_OK || nq == 0) return rc;
-  return host_round_trip(t, q, nq, counts, (size_t)nq * sizeof(uint64_t), [&](const float* d_q, char* d_out, hipStream_t s) {
-    return ptk_search_count_within_device(t, d_q, nq, radius, max_count, reinterpret_cast<uint64_t*>(d_out), s);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)nq * sizeof(uint64_t))};
+  return host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_search_count_within_device(t, in.at<float>(d_in, 0), nq, radius, max_count, out.at<uint64_t>(d_out, 0), s);
   });
 }
 
@@ -2136,13 +2124,12 @@ int ptk_search_count_within_radii(const ptk_tree* t, const float* q, uint64_t nq
                                   uint64_t* counts) {
   const int rc = check_count_within_radii(t, q, nq, radii, counts, /*host_values=*/true);
   if (rc != PTK_OK || nq == 0) return rc;
-  const float* d_radii = nullptr;
-  return host_round_trip(
-      t, q, nq, counts, (size_t)nq * sizeof(uint64_t),
-      [&](const float* d_q, char* d_out, hipStream_t s) {
-        return ptk_search_count_within_radii_device(t, d_q, nq, d_radii, max_count, reinterpret_cast<uint64_t*>(d_out), s);
-      },
-      radii, &d_radii);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(float)), ptkio::in_part(radii, (size_t)nq * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)nq * sizeof(uint64_t))};
+  return host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_search_count_within_radii_device(t, in.at<float>(d_in, 0), nq, in.at<float>(d_in, 1), max_count,
+                                                out.at<uint64_t>(d_out, 0), s);
+  });
 }
 
 // ---- radius -------------------------------------------------------------------------------
@@ -2438,29 +2425,11 @@ int ptk_search_count_within_self(const ptk_tree* t, float radius, const float* r
   const int rc = check_radius_self(t, radius, radii, /*host_values=*/true, counts, "count_within_self",
                                    "ptk_host_search_count_within_self");
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t out_bytes = (size_t)t->n_points * sizeof(uint64_t);
-  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
-  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
-  if (src != PTK_OK) return src;
-  const float* d_radii = nullptr;
-  if (radii != nullptr) {
-    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
-    d_radii = reinterpret_cast<const float*>(io.d_in);
-  }
-  src = ptk_search_count_within_self_device(t, radius, d_radii, max_count, reinterpret_cast<uint64_t*>(io.d_out), io.search[0]);
-  if (src != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
-    return src;
-  }
-  PTK_HIP(hipMemcpyAsync(counts, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
-  return PTK_OK;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)t->n_points * sizeof(uint64_t))};
+  return host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_search_count_within_self_device(t, radius, in.at<float>(d_in, 0), max_count, out.at<uint64_t>(d_out, 0), s);
+  });
 }
 
 // Convenience, as ptk_search_radius_radii: the count, the scan and the fill on the device.
@@ -2536,30 +2505,13 @@ int ptk_cluster_within_self(const ptk_tree* t, float radius, const float* radii,
   const int rc = check_radius_self(t, radius, radii, /*host_values=*/true, labels, "cluster_within_self",
                                    "ptk_host_cluster_within_self");
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t out_bytes = (size_t)t->n_points * sizeof(int32_t);
-  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int src = grow_device_block(&io.d_out, &io.out_capacity, out_bytes);
-  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
-  if (src != PTK_OK) return src;
-  const float* d_radii = nullptr;
-  if (radii != nullptr) {
-    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
-    d_radii = reinterpret_cast<const float*>(io.d_in);
-  }
-  src = ptk_cluster_within_self_device(t, radius, d_radii, min_neighbors, reinterpret_cast<int32_t*>(io.d_out), io.search[0]);
-  if (src != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
-    return src;
-  }
-  PTK_HIP(hipMemcpyAsync(labels, io.d_out, out_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
-  if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
-  return PTK_OK;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(labels, (size_t)t->n_points * sizeof(int32_t))};
+  const int src = host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_cluster_within_self_device(t, radius, in.at<float>(d_in, 0), min_neighbors, out.at<int32_t>(d_out, 0), s);
+  });
+  if (src == PTK_OK && n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
+  return src;
 }
 
 // ---- normals_within_self (ptk.h; the kernel: ptk_kernels_frames.hpp) ----------------------------------------
@@ -2583,35 +2535,13 @@ int ptk_normals_within_self(const ptk_tree* t, float radius, const float* radii,
                             const float* viewpoint, ptk_frame* frames, ptk_moments* moments) {
   const int rc = check_normals_self(t, radius, radii, /*host_values=*/true, frames, moments);
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const size_t frame_bytes = frames != nullptr ? (size_t)t->n_points * sizeof(ptk_frame) : 0;
-  const size_t moment_bytes = moments != nullptr ? (size_t)t->n_points * sizeof(ptk_moments) : 0;
-  const size_t radii_bytes = radii != nullptr ? (size_t)t->n_points * sizeof(float) : 0;
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  int src = grow_device_block(&io.d_out, &io.out_capacity, frame_bytes + moment_bytes);
-  if (src == PTK_OK && radii != nullptr) src = grow_device_block(&io.d_in, &io.in_capacity, radii_bytes);
-  if (src != PTK_OK) return src;
-  const float* d_radii = nullptr;
-  if (radii != nullptr) {
-    PTK_HIP(hipMemcpyAsync(io.d_in, radii, radii_bytes, hipMemcpyHostToDevice, io.search[0]));
-    d_radii = reinterpret_cast<const float*>(io.d_in);
-  }
-  // (the frames first: a run of 32-byte records keeps the moments behind it 16-byte aligned)
-  char* base = reinterpret_cast<char*>(io.d_out);
-  auto* d_frames = frames != nullptr ? reinterpret_cast<ptk_frame*>(base) : nullptr;
-  auto* d_moments = moments != nullptr ? reinterpret_cast<ptk_moments*>(base + frame_bytes) : nullptr;
-  src = ptk_normals_within_self_device(t, radius, d_radii, min_neighbors, viewpoint, d_frames, d_moments, io.search[0]);
-  if (src != PTK_OK) {
-    (void)hipStreamSynchronize(io.search[0]);
-    return src;
-  }
-  if (frames != nullptr) PTK_HIP(hipMemcpyAsync(frames, d_frames, frame_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  if (moments != nullptr) PTK_HIP(hipMemcpyAsync(moments, d_moments, moment_bytes, hipMemcpyDeviceToHost, io.search[0]));
-  PTK_HIP(hipStreamSynchronize(io.search[0]));
-  return PTK_OK;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(frames, (size_t)t->n_points * sizeof(ptk_frame)),
+                         ptkio::out_part(moments, (size_t)t->n_points * sizeof(ptk_moments))};
+  return host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_normals_within_self_device(t, radius, in.at<float>(d_in, 0), min_neighbors, viewpoint,
+                                          out.at<ptk_frame>(d_out, 0), out.at<ptk_moments>(d_out, 1), s);
+  });
 }
 
 // ---- aggregate_within_self / aggregate_within (ptk.h; the kernels: ptk_kernels_aggregate.hpp) ---------------
@@ -2647,62 +2577,31 @@ int ptk_aggregate_within_device(const ptk_tree* t, const float* d_q, uint64_t nq
   return ptkf::aggregate_within(t, d_q, perm, nq, radius, d_radii, d_values, channels, op, d_out, d_counts, s);
 }
 
-// The host-buffer forms: the values, then the queries and the radii go up in the handle's input block (each part on a
-// 16-byte boundary), `out` and the counts come down from its output block.  q null: the self form.
-static int aggregate_round_trip(const ptk_tree* t, const float* q, uint64_t nq, float radius, const float* radii,
-                                const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts) {
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  const bool self_form = q == nullptr;
-  const uint64_t rows = self_form ? t->n_points : nq;
-  const auto pad16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t value_bytes = (size_t)t->n_points * channels * sizeof(float);
-  const size_t q_bytes = self_form ? 0 : (size_t)nq * t->dim * sizeof(float);
-  const size_t radii_bytes = radii != nullptr ? (size_t)rows * sizeof(float) : 0;
-  const size_t out_bytes = (size_t)rows * channels * sizeof(float);
-  const size_t count_bytes = counts != nullptr ? (size_t)rows * sizeof(uint64_t) : 0;
-  HostIo& io = t->io;
-  std::lock_guard<std::mutex> lock(io.mutex);
-  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
-  hipStream_t s = io.search[0];
-  int rc = grow_device_block(&io.d_in, &io.in_capacity, pad16(value_bytes) + pad16(q_bytes) + radii_bytes);
-  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, pad16(out_bytes) + count_bytes);
-  if (rc != PTK_OK) return rc;
-  char* d_values = io.d_in;
-  char* d_q = d_values + pad16(value_bytes);
-  char* d_radii = d_q + pad16(q_bytes);
-  PTK_HIP(hipMemcpyAsync(d_values, values, value_bytes, hipMemcpyHostToDevice, s));
-  if (!self_form) PTK_HIP(hipMemcpyAsync(d_q, q, q_bytes, hipMemcpyHostToDevice, s));
-  if (radii != nullptr) PTK_HIP(hipMemcpyAsync(d_radii, radii, radii_bytes, hipMemcpyHostToDevice, s));
-  const float* dr = radii != nullptr ? reinterpret_cast<const float*>(d_radii) : nullptr;
-  auto* d_out = reinterpret_cast<float*>(io.d_out);
-  auto* d_counts = counts != nullptr ? reinterpret_cast<uint64_t*>(io.d_out + pad16(out_bytes)) : nullptr;
-  rc = self_form ? ptk_aggregate_within_self_device(t, radius, dr, reinterpret_cast<const float*>(d_values), channels, op,
-                                                    d_out, d_counts, s)
-                 : ptk_aggregate_within_device(t, reinterpret_cast<const float*>(d_q), nq, radius, dr,
-                                               reinterpret_cast<const float*>(d_values), channels, op, d_out, d_counts, s);
-  if (rc != PTK_OK) {
-    (void)hipStreamSynchronize(s);
-    return rc;
-  }
-  PTK_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-  if (counts != nullptr) PTK_HIP(hipMemcpyAsync(counts, d_counts, count_bytes, hipMemcpyDeviceToHost, s));
-  PTK_HIP(hipStreamSynchronize(s));
-  return PTK_OK;
-}
-
+// The host-buffer forms: the values, the queries (the query form) and the radii go up, `out` and the counts come down.
 int ptk_aggregate_within_self(const ptk_tree* t, float radius, const float* radii, const float* values, uint32_t channels,
                               uint32_t op, float* out, uint64_t* counts) {
   const int rc = check_aggregate_self(t, radius, radii, /*host_values=*/true, values, channels, op, out);
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  return aggregate_round_trip(t, nullptr, 0, radius, radii, values, channels, op, out, counts);
+  const uint64_t np = t->n_points;
+  const ptkio::Parts in{ptkio::in_part(values, (size_t)np * channels * sizeof(float)), ptkio::in_part(radii, (size_t)np * sizeof(float))};
+  const ptkio::Parts res{ptkio::out_part(out, (size_t)np * channels * sizeof(float)), ptkio::out_part(counts, (size_t)np * sizeof(uint64_t))};
+  return host_form(t, in, res, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_aggregate_within_self_device(t, radius, in.at<float>(d_in, 1), in.at<float>(d_in, 0), channels, op,
+                                            res.at<float>(d_out, 0), res.at<uint64_t>(d_out, 1), s);
+  });
 }
 
 int ptk_aggregate_within(const ptk_tree* t, const float* q, uint64_t nq, float radius, const float* radii,
                          const float* values, uint32_t channels, uint32_t op, float* out, uint64_t* counts) {
   const int rc = check_aggregate_within(t, q, nq, radius, radii, /*host_values=*/true, values, channels, op, out);
   if (rc != PTK_OK || nq == 0) return rc;
-  return aggregate_round_trip(t, q, nq, radius, radii, values, channels, op, out, counts);
+  const ptkio::Parts in{ptkio::in_part(values, (size_t)t->n_points * channels * sizeof(float)),
+                        ptkio::in_part(q, (size_t)nq * t->dim * sizeof(float)), ptkio::in_part(radii, (size_t)nq * sizeof(float))};
+  const ptkio::Parts res{ptkio::out_part(out, (size_t)nq * channels * sizeof(float)), ptkio::out_part(counts, (size_t)nq * sizeof(uint64_t))};
+  return host_form(t, in, res, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_aggregate_within_device(t, in.at<float>(d_in, 1), nq, radius, in.at<float>(d_in, 2), in.at<float>(d_in, 0),
+                                       channels, op, res.at<float>(d_out, 0), res.at<uint64_t>(d_out, 1), s);
+  });
 }
 
 }  // extern "C"

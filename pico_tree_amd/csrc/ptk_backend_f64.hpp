@@ -11,6 +11,7 @@
 #include "ptk_kernels_f64.hpp"
 #include "ptk_kernels_coop64.hpp"
 #include "ptk_rows_out.hpp"
+#include "ptk_io_parts.hpp"
 
 static_assert(sizeof(ptk_neighbor64) == 16 && offsetof(ptk_neighbor64, distance) == 8, "neighbor<int, double> layout");
 
@@ -229,32 +230,28 @@ auto rows_in(const ptk_tree64* t, IoBuffer& block) {
   };
 }
 
-// The host-buffer form of a search whose rows have one size: under the handle's I/O lock the batch goes up into block 0,
-// `search(d_q, d_out)` -- the _device form, on the null stream -- fills block 1, and that comes down.  `records`: the rows
-// are ptk_neighbor64 records, whose padding bytes no kernel writes: the block is cleared first.
+// The host-buffer form of every call whose rows have one size, written once: under the handle's I/O lock the input parts
+// go up into block 0, `search(d_in, d_out)` -- the _device form, on the null stream, which finds its device pointers with
+// in.at<T>(d_in, i) and out.at<T>(d_out, i) -- fills block 1, and the output parts come down (blocking copies
+// throughout).  An output part marked clear_first holds ptk_neighbor64 records, whose padding bytes no kernel writes: it
+// is zeroed before the search.  An absent part (ptk_io_parts.hpp) is neither copied nor given room.
 template <class Search>
-int host_round_trip64(const ptk_tree64* t, const double* q, uint64_t nq, void* out, size_t out_bytes, bool records,
-                      Search&& search, const double* radii = nullptr, const double** d_radii = nullptr) {
+int host_form64(const ptk_tree64* t, const ptkio::Parts& in, const ptkio::Parts& out, Search&& search) {
   DeviceGuard guard(t->device);
   if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
   std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bq, bo;
-  const size_t qbytes = (size_t)nq * t->dim * sizeof(double);
-  // (the _radii forms: the nq radii travel behind the queries in the same block)
-  const size_t rbytes = radii != nullptr ? (size_t)nq * sizeof(double) : 0;
-  hipError_t he = bq.get(t, 0, qbytes + rbytes);
-  if (he == hipSuccess) he = bo.get(t, 1, out_bytes);
-  if (he == hipSuccess && records) he = hipMemset(bo.p, 0, out_bytes ? out_bytes : 16);
-  if (he == hipSuccess) he = hipMemcpy(bq.p, q, qbytes, hipMemcpyHostToDevice);
-  if (he == hipSuccess && radii != nullptr) {
-    he = hipMemcpy(bq.p + qbytes, radii, rbytes, hipMemcpyHostToDevice);
-    *d_radii = reinterpret_cast<const double*>(bq.p + qbytes);
-  }
+  IoBuffer bin, bout;
+  hipError_t he = in.any() ? bin.get(t, 0, in.total()) : hipSuccess;
+  if (he == hipSuccess && out.any()) he = bout.get(t, 1, out.total());
+  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (the buffers of a host-buffer call): %s", hipGetErrorString(he));
+  for (int i = 0; i < out.size() && he == hipSuccess; ++i)
+    if (out.clear_first(i) && out.bytes(i) != 0) he = hipMemset(bout.p + out.offset(i), 0, out.bytes(i));
+  for (int i = 0; i < in.size() && he == hipSuccess; ++i)
+    if (in.present(i)) he = hipMemcpy(bin.p + in.offset(i), in.source(i), in.bytes(i), hipMemcpyHostToDevice);
   int rc = PTK_OK;
-  if (he == hipSuccess) {
-    rc = search(reinterpret_cast<const double*>(bq.p), bo.p);
-    if (rc == PTK_OK) he = hipMemcpy(out, bo.p, out_bytes, hipMemcpyDeviceToHost);
-  }
+  if (he == hipSuccess) rc = search(bin.p, bout.p);
+  for (int i = 0; i < out.size() && he == hipSuccess && rc == PTK_OK; ++i)
+    if (out.present(i)) he = hipMemcpy(out.destination(i), bout.p + out.offset(i), out.bytes(i), hipMemcpyDeviceToHost);
   if (rc == PTK_OK && he != hipSuccess) rc = fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return rc;
 }
@@ -961,18 +958,11 @@ int ptk_search64_knn_self_device(const ptk_tree64* t, uint32_t k, ptk_neighbor64
 int ptk_search64_knn_self(const ptk_tree64* t, uint32_t k, ptk_neighbor64* out) {
   const int rc = check_knn_self(t, k, out);
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bo;  // (nothing goes up: the rows come down only)
-  const size_t out_bytes = (size_t)t->n_points * k * sizeof(ptk_neighbor64);
-  hipError_t he = bo.get(t, 1, out_bytes);
-  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (%zu bytes of rows): %s", out_bytes, hipGetErrorString(he));
-  const int src = ptk_search64_knn_self_device(t, k, reinterpret_cast<ptk_neighbor64*>(bo.p), nullptr);
-  if (src != PTK_OK) return src;
-  he = hipMemcpy(out, bo.p, out_bytes, hipMemcpyDeviceToHost);
-  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  return PTK_OK;
+  // (nothing goes up: the rows come down only)
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)t->n_points * k * sizeof(ptk_neighbor64))};
+  return host_form64(t, ptkio::Parts{}, rows, [&](char*, char* d_out) {
+    return ptk_search64_knn_self_device(t, k, rows.at<ptk_neighbor64>(d_out, 0), nullptr);
+  });
 }
 
 // search_knn_within (ptk.h).  The list starts at radius * (1 + 2^-10) (as the float32 search); DBL_MAX
@@ -1005,11 +995,11 @@ int ptk_search64_knn_within(const ptk_tree64* t, const double* q, uint64_t nq, u
                             ptk_neighbor64* out) {
   const int rc = check_knn_within(t, q, nq, k, radius, out);
   if (rc != PTK_OK || nq == 0) return rc;
-  return host_round_trip64(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
-                           [&](const double* d_q, char* d_out) {
-                             return ptk_search64_knn_within_device(t, d_q, nq, k, radius,
-                                                                   reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
-                           });
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(double))};
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)nq * k * sizeof(ptk_neighbor64), /*clear_first=*/true)};
+  return host_form64(t, in, rows, [&](char* d_in, char* d_out) {
+    return ptk_search64_knn_within_device(t, in.at<double>(d_in, 0), nq, k, radius, rows.at<ptk_neighbor64>(d_out, 0), nullptr);
+  });
 }
 
 // search_knn_within_radii (ptk.h): the same launch with the per-row kernels; each lane derives its seed
@@ -1038,13 +1028,12 @@ int ptk_search64_knn_within_radii(const ptk_tree64* t, const double* q, uint64_t
                                   ptk_neighbor64* out) {
   const int rc = check_knn_within_radii(t, q, nq, k, radii, out, /*host_values=*/true);
   if (rc != PTK_OK || nq == 0) return rc;
-  const double* d_radii = nullptr;
-  return host_round_trip64(
-      t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
-      [&](const double* d_q, char* d_out) {
-        return ptk_search64_knn_within_radii_device(t, d_q, nq, k, d_radii, reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
-      },
-      radii, &d_radii);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(double)), ptkio::in_part(radii, (size_t)nq * sizeof(double))};
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)nq * k * sizeof(ptk_neighbor64), /*clear_first=*/true)};
+  return host_form64(t, in, rows, [&](char* d_in, char* d_out) {
+    return ptk_search64_knn_within_radii_device(t, in.at<double>(d_in, 0), nq, k, in.at<double>(d_in, 1),
+                                                rows.at<ptk_neighbor64>(d_out, 0), nullptr);
+  });
 }
 
 // count_within (ptk.h): dim <= 3 and the four non-topological metrics take count64_within_kernel (the
@@ -1100,11 +1089,11 @@ int ptk_search64_count_within(const ptk_tree64* t, const double* q, uint64_t nq,
                               uint64_t* counts) {
   const int rc = check_count_within(t, q, nq, radius, counts);
   if (rc != PTK_OK || nq == 0) return rc;
-  return host_round_trip64(t, q, nq, counts, (size_t)nq * sizeof(uint64_t), /*records=*/false,
-                           [&](const double* d_q, char* d_out) {
-                             return ptk_search64_count_within_device(t, d_q, nq, radius, max_count,
-                                                                     reinterpret_cast<uint64_t*>(d_out), nullptr);
-                           });
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(double))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)nq * sizeof(uint64_t))};
+  return host_form64(t, in, out, [&](char* d_in, char* d_out) {
+    return ptk_search64_count_within_device(t, in.at<double>(d_in, 0), nq, radius, max_count, out.at<uint64_t>(d_out, 0), nullptr);
+  });
 }
 
 // count_within_radii (ptk.h): the side-table kernel with a radius per row; the handles the scalar call serves through
@@ -1134,14 +1123,12 @@ int ptk_search64_count_within_radii(const ptk_tree64* t, const double* q, uint64
                                     uint64_t max_count, uint64_t* counts) {
   const int rc = check_count_within_radii(t, q, nq, radii, counts, /*host_values=*/true);
   if (rc != PTK_OK || nq == 0) return rc;
-  const double* d_radii = nullptr;
-  return host_round_trip64(
-      t, q, nq, counts, (size_t)nq * sizeof(uint64_t), /*records=*/false,
-      [&](const double* d_q, char* d_out) {
-        return ptk_search64_count_within_radii_device(t, d_q, nq, d_radii, max_count, reinterpret_cast<uint64_t*>(d_out),
-                                                      nullptr);
-      },
-      radii, &d_radii);
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(double)), ptkio::in_part(radii, (size_t)nq * sizeof(double))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)nq * sizeof(uint64_t))};
+  return host_form64(t, in, out, [&](char* d_in, char* d_out) {
+    return ptk_search64_count_within_radii_device(t, in.at<double>(d_in, 0), nq, in.at<double>(d_in, 1), max_count,
+                                                  out.at<uint64_t>(d_out, 0), nullptr);
+  });
 }
 
 int ptk_tree64_debug_knn_coop_counts(const ptk_tree64* t, uint32_t counts[7]) {
@@ -1169,10 +1156,11 @@ int ptk_search64_knn(const ptk_tree64* t, const double* q, uint64_t nq, uint32_t
   const int rc = check_search(t, q, nq);
   if (rc != PTK_OK || nq == 0) return rc;
   if (out == nullptr) return fail(PTK_ERR_INVALID, "null output buffer");
-  return host_round_trip64(t, q, nq, out, (size_t)nq * k * sizeof(ptk_neighbor64), /*records=*/true,
-                           [&](const double* d_q, char* d_out) {
-                             return ptk_search64_knn_device(t, d_q, nq, k, e, reinterpret_cast<ptk_neighbor64*>(d_out), nullptr);
-                           });
+  const ptkio::Parts in{ptkio::in_part(q, (size_t)nq * t->dim * sizeof(double))};
+  const ptkio::Parts rows{ptkio::out_part(out, (size_t)nq * k * sizeof(ptk_neighbor64), /*clear_first=*/true)};
+  return host_form64(t, in, rows, [&](char* d_in, char* d_out) {
+    return ptk_search64_knn_device(t, in.at<double>(d_in, 0), nq, k, e, rows.at<ptk_neighbor64>(d_out, 0), nullptr);
+  });
 }
 
 int ptk_search64_radius(const ptk_tree64* t, const double* q, uint64_t nq, double radius, double e, int sort,
@@ -1318,24 +1306,11 @@ int ptk_search64_count_within_self(const ptk_tree64* t, double radius, const dou
   int rc = check_radius_self(t, radius, radii, /*host_values=*/true, counts, "count_within_self",
                              "kd_tree::search_radius_self, one point at a time");
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bin, bout;
-  const uint64_t np = t->n_points;
-  hipError_t he = bout.get(t, 1, np * 8);
-  const double* d_radii = nullptr;
-  if (he == hipSuccess && radii != nullptr) {
-    he = bin.get(t, 0, np * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpy(bin.p, radii, np * sizeof(double), hipMemcpyHostToDevice);
-    d_radii = reinterpret_cast<const double*>(bin.p);
-  }
-  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (the buffers of count_within_self): %s", hipGetErrorString(he));
-  rc = ptk_search64_count_within_self_device(t, radius, d_radii, max_count, reinterpret_cast<uint64_t*>(bout.p), nullptr);
-  if (rc != PTK_OK) return rc;
-  he = hipMemcpy(counts, bout.p, np * 8, hipMemcpyDeviceToHost);
-  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  return PTK_OK;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(double))};
+  const ptkio::Parts out{ptkio::out_part(counts, (size_t)t->n_points * sizeof(uint64_t))};
+  return host_form64(t, in, out, [&](char* d_in, char* d_out) {
+    return ptk_search64_count_within_self_device(t, radius, in.at<double>(d_in, 0), max_count, out.at<uint64_t>(d_out, 0), nullptr);
+  });
 }
 
 // ptk_search_radius_self in double: the count (max_count = 0), the scan and the fill on the device.
@@ -1419,25 +1394,13 @@ int ptk_search64_cluster_within_self(const ptk_tree64* t, double radius, const d
   int rc = check_radius_self(t, radius, radii, /*host_values=*/true, labels, "cluster_within_self",
                              "kd_tree::cluster_within_self, one point at a time");
   if (rc != PTK_OK || t->n_points == 0) return rc;
-  DeviceGuard guard(t->device);
-  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
-  std::lock_guard<std::mutex> io_lock(t->io_mutex);
-  IoBuffer bin, bout;
-  const uint64_t np = t->n_points;
-  hipError_t he = bout.get(t, 1, np * sizeof(int32_t));
-  const double* d_radii = nullptr;
-  if (he == hipSuccess && radii != nullptr) {
-    he = bin.get(t, 0, np * sizeof(double));
-    if (he == hipSuccess) he = hipMemcpy(bin.p, radii, np * sizeof(double), hipMemcpyHostToDevice);
-    d_radii = reinterpret_cast<const double*>(bin.p);
-  }
-  if (he != hipSuccess) return fail(PTK_ERR_NOMEM, "out of device memory (the buffers of cluster_within_self): %s", hipGetErrorString(he));
-  rc = ptk_search64_cluster_within_self_device(t, radius, d_radii, min_neighbors, reinterpret_cast<int32_t*>(bout.p), nullptr);
-  if (rc != PTK_OK) return rc;
-  he = hipMemcpy(labels, bout.p, np * sizeof(int32_t), hipMemcpyDeviceToHost);
-  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
-  if (n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, np);
-  return PTK_OK;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(double))};
+  const ptkio::Parts out{ptkio::out_part(labels, (size_t)t->n_points * sizeof(int32_t))};
+  rc = host_form64(t, in, out, [&](char* d_in, char* d_out) {
+    return ptk_search64_cluster_within_self_device(t, radius, in.at<double>(d_in, 0), min_neighbors, out.at<int32_t>(d_out, 0), nullptr);
+  });
+  if (rc == PTK_OK && n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
+  return rc;
 }
 
 int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs, uint64_t nb, uint64_t* offsets,
