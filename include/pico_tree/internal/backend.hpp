@@ -225,6 +225,10 @@ struct ptk_api<float> {
                                    std::uint32_t channels, std::uint32_t op, float* out, std::uint64_t* counts) {
     return ptk_aggregate_within_self(t, radius, radii, values, channels, op, out, counts);
   }
+  static int align_step(tree const* t, float const* q, std::uint64_t nq, float const* transform, float max_distance,
+                        float const* normals, ptk_align_sums* out, neighbor* rows) {
+    return ptk_align_step(t, q, nq, transform, max_distance, normals, out, rows);
+  }
   static int aggregate_within(tree const* t, float const* q, std::uint64_t nq, float radius, float const* radii,
                               float const* values, std::uint32_t channels, std::uint32_t op, float* out,
                               std::uint64_t* counts) {

@@ -33,6 +33,7 @@
 #include "internal/access.hpp"
 #include "internal/backend.hpp"
 #include "internal/aggregate.hpp"
+#include "internal/align.hpp"
 #include "internal/cluster.hpp"
 #include "internal/flat_search.hpp"
 #include "internal/flat_tree.hpp"
@@ -535,6 +536,28 @@ class kd_tree {
     batched_aggregate_within(queries, scalar_type(0), &radii, values, channels, op, out, counts);
   }
 
+  //! The normal equations of one ICP iteration (float points, three
+  //! dimensions, metric_l2_squared).  Each query is posed by \p transform (12
+  //! scalars, row-major [R|t], applied in float32; null: as it is), matched to
+  //! its nearest tree point (search_knn with k = 1), rejected where the squared
+  //! distance is not below \p max_distance, and the terms of the accepted rows
+  //! are summed in double in the fixed order of internal/align.hpp: the
+  //! point-to-point sums without \p normals, the point-to-plane sums with them
+  //! (size() x 3 scalars by original point index).  \p rows, if given, receives
+  //! the unfiltered rows.  Served by the backend (ptk_align_step); where it
+  //! refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined, by the per-point member with the routines of
+  //! internal/align.hpp: the same bytes either way.
+  template <typename QuerySpace_>
+  inline align_sums align_step(
+      QuerySpace_ const& queries,
+      scalar_type const* transform,
+      scalar_type const max_distance,
+      scalar_type const* normals = nullptr,
+      std::vector<neighbor_type>* rows = nullptr) const {
+    return batched_align_step(queries, transform, max_distance, normals, rows);
+  }
+
   //! counts[i] = count_within(query i, radius), clamped to \p max_count when
   //! that is > 0.  \p radius must be >= 0 and not NaN.
   template <typename QuerySpace_>
@@ -1030,6 +1053,68 @@ class kd_tree {
       rows_loop();
     }
 #endif
+  }
+
+  template <typename QuerySpace_>
+  align_sums batched_align_step(
+      QuerySpace_ const& queries,
+      scalar_type const* transform,
+      scalar_type max_distance,
+      scalar_type const* normals,
+      std::vector<neighbor_type>* rows) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(std::is_same_v<scalar_type, float>, "ALIGN_STEP_NEEDS_FLOAT_POINTS");
+    static_assert(std::is_same_v<Metric_, metric_l2_squared>, "ALIGN_STEP_NEEDS_METRIC_L2_SQUARED");
+    static_assert(sizeof(neighbor_type) == sizeof(typename api::neighbor), "neighbor layout");
+    auto const points = view();
+    if (points.sdim() != 3) throw std::invalid_argument("pico_tree: align_step needs 3-D points");
+    internal::dense_rows<internal::unwrap_ref_t<QuerySpace_>> q(unwrap(queries));
+    check_query_dim(q.cols());
+    if (!(max_distance >= scalar_type(0))) throw std::invalid_argument("pico_tree: align_step needs max_distance >= 0");
+    size_type const n = q.rows();
+    std::vector<neighbor_type> own;
+    std::vector<neighbor_type>& found = rows != nullptr ? *rows : own;
+    found.resize(n);
+    align_sums out;
+    auto const rows_loop = [&]() {
+      std::vector<float> posed;
+      float const* qp = q.data();
+      if (transform != nullptr && n > 0) {
+        posed.resize(n * 3);
+        internal::host_rows_loop(n, [&](size_type i) {
+          internal::align_pose(transform, q.data()[3 * i], q.data()[3 * i + 1], q.data()[3 * i + 2], &posed[3 * i]);
+        });
+        qp = posed.data();
+      }
+      // (a slot the search did not write holds {0, FLT_MAX}, as the backend's rows)
+      using row_point = point_map<scalar_type const, dim>;
+      internal::host_rows_loop(n, [&](size_type i) {
+        found[i] = neighbor_type{0, std::numeric_limits<scalar_type>::max()};
+        row_point x = make_row(qp + i * 3, 3);
+        search_knn(x, &found[i], &found[i] + 1);
+      });
+      internal::align_reduce_rows(
+          qp, n, [&](std::uint64_t i, std::int32_t& index, float& distance) { index = found[i].index, distance = found[i].distance; },
+          [&](std::int32_t index) { return points[static_cast<index_type>(index)]; }, normals, max_distance,
+          [](std::uint64_t blocks, auto&& f) { internal::host_rows_loop(blocks, [&](size_type b) { f(b); }); }, &out);
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    static_assert(sizeof(align_sums) == sizeof(ptk_align_sums), "record layout");
+    try {
+      internal::ptk_check(
+          api::align_step(
+              device(), q.data(), n, transform, max_distance, normals, reinterpret_cast<ptk_align_sums*>(&out),
+              reinterpret_cast<typename api::neighbor*>(found.data())),
+          "ptk_align_step");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+    return out;
   }
 
   void check_aggregate(scalar_type const* values, size_type channels) const {

@@ -597,6 +597,66 @@ int ptk_aggregate_within_device(const ptk_tree* tree, const float* d_queries, ui
                                 const float* d_values, uint32_t channels, uint32_t op, float* d_out, uint64_t* d_counts,
                                 void* stream);
 
+/* ---- align_step: the normal equations of one ICP iteration --------------------------------------------------------------
+ * One call poses the source points, runs the k = 1 search, rejects rows by distance and leaves the double-precision sums
+ * of one registration step on the device: from them the rigid motion follows on the host, by an SVD (point-to-point) or a
+ * 6 x 6 solve (point-to-plane, with the target's normals).  float32 trees with dim == 3 under metric_l2_squared.  Every
+ * operation named below is exactly one IEEE operation of the stated width: no contraction, no reassociation.  Contract
+ * (DESIGN.md section 2):
+ *   Pose.  q'_a = ((R_a0*q_x + R_a1*q_y) + R_a2*q_z) + t_a in float32, `transform` being 12 host floats, row-major
+ * [R|t], read at the call (as `viewpoint` is in ptk_normals_within_self).  transform == NULL: q' = q, no arithmetic.
+ *   Row.  Row i is ptk_search_knn(q'_i, k = 1, e = 1) on the handle: the same index, the same distance bits.  `rows`
+ * (`d_rows`), when given, receives these nq rows, unfiltered.
+ *   Acceptance.  Row i is accepted iff distance < max_distance (strict, as the radius searches) and distance < FLT_MAX.
+ * The second test excludes the {0, FLT_MAX} pad and every NaN, infinite or overflowing row.  With normals, the three
+ * components of the matched point's normal must be finite as well.  max_distance is in metric units (squared); +inf is
+ * valid; NaN or a negative value is PTK_ERR_INVALID.  A rejected row contributes +0.0 to every sum and 0 to `count`.
+ *   Terms.  q, p, n: the float32 values q'_i, the matched tree point (the caller's bits) and its normal
+ * (target_normals[index], [n_points, 3] by ORIGINAL index), converted to double; double operations from there.
+ *     point-to-point (normals NULL)   sum_q[a] <- q_a   sum_p[a] <- p_a   sum_qp[3a+b] <- q_a*p_b
+ *                                     sum_qq <- (q_x*q_x + q_y*q_y) + q_z*q_z   sum_pp likewise
+ *     point-to-plane                  e_a = q_a - p_a   r = ((e_x*n_x) + (e_y*n_y)) + (e_z*n_z)
+ *                                     c_x = (q_y*n_z) - (q_z*n_y)  c_y = (q_z*n_x) - (q_x*n_z)  c_z = (q_x*n_y) - (q_y*n_x)
+ *                                     J = (c_x, c_y, c_z, n_x, n_y, n_z)
+ *                                     jtj[u <= v] <- J_u*J_v (upper triangle, row-major)   jtr[u] <- J_u*r   sum_rr <- r*r
+ *     both                            sum_distance <- (double)distance
+ * The sums of the other mode are +0.
+ *   Order of the sums.  Each sum is a fixed tree over the caller's row order.  Level 0 cuts the rows into blocks of 256
+ * consecutive rows, entries past the end being +0.0.  In a block, lane l (0..63) computes
+ * ((((+0.0 + x[l]) + x[l+64]) + x[l+128]) + x[l+192]); then for s = 32, 16, 8, 4, 2, 1: v[l] = v[l] + v[l+s] for l < s;
+ * v[0] is the block's partial.  The partials of a level, in block order, are the entries of the next; levels repeat until
+ * one value is left (a batch of one row takes one level).  `count` is an integer sum.  nq == 0 writes all zeros.  The
+ * result does not depend on PTK_MAX_BATCH, on the batch order of the search, on the launch geometry or on the form:
+ * device form, host form, host loop and kd_tree::align_step give identical bytes, and so do two calls.
+ *   Arguments.  A null `out` is PTK_ERR_INVALID; with nq > 0 so are a null queries pointer and, in the device form, a null
+ * workspace or one smaller than ptk_align_step_workspace says (the message gives both sizes).
+ *   Handles.  dim != 3 or another metric is PTK_ERR_INVALID from every form, the host loop included.  Within those
+ * handles the device serves whatever ptk_search_knn_device serves with k = 1 -- piles and the deep stack class included --
+ * and passes a refusal of the search on unchanged.  A host-only handle: PTK_ERR_DEVICE.
+ *   State.  The device form only enqueues on `stream`.  Its temporaries -- q', the rows when d_rows is NULL, the partials
+ * of every level -- live in the caller's workspace; the search takes the handle's per-stream scratch as
+ * ptk_search_knn_device does.  The one exception: the first call on a handle builds the inverse of the leaf permutation
+ * (uint32 per point, one scatter kernel) and waits for it; the handle keeps it, as it keeps the count side table.  The
+ * radius capture is neither read nor invalidated.  d_out is written with plain vector stores.  The host form uploads the
+ * queries and the normals and downloads the record and, if asked, the rows. */
+typedef struct ptk_align_sums {
+  uint64_t count;        /* accepted rows */
+  uint64_t rows;         /* nq */
+  double sum_distance;   /* sum of (double)row distance over accepted rows */
+  /* point-to-point (normals == NULL); all +0 in plane mode */
+  double sum_q[3], sum_p[3], sum_qp[9] /* [a*3+b] = sum q_a p_b */, sum_qq, sum_pp;
+  /* point-to-plane (normals != NULL); all +0 otherwise */
+  double jtj[21] /* upper triangle, row-major */, jtr[6], sum_rr;
+} ptk_align_sums; /* 384 bytes */
+int ptk_align_step_workspace(const ptk_tree* tree, uint64_t nq, uint64_t* bytes);
+int ptk_align_step_device(const ptk_tree* tree, const float* d_queries, uint64_t nq,
+                          const float* transform /* host, 12 floats row-major [R|t], or NULL */, float max_distance,
+                          const float* d_target_normals /* [n_points,3] by ORIGINAL index, or NULL */,
+                          ptk_align_sums* d_out, ptk_neighbor* d_rows /* nq, or NULL */, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
+int ptk_align_step(const ptk_tree* tree, const float* queries, uint64_t nq, const float* transform, float max_distance,
+                   const float* target_normals, ptk_align_sums* out, ptk_neighbor* rows);
+
 /* ---- box search (ragged output) --------------------------------------- */
 /* mins / maxs: nb x dim.  Row i lists the indices inside [min_i, max_i]
  * (closed), in reference traversal order. */
@@ -667,6 +727,11 @@ int ptk_host_aggregate_within_self(const ptk_tree* tree, const float* points, fl
 int ptk_host_aggregate_within(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, float radius,
                               const float* radii, const float* values, uint32_t channels, uint32_t op, float* out,
                               uint64_t* counts);
+/* (ptk_align_step as the contract reads: the pose on the host, the rows of ptk_host_search_knn with k = 1, then the terms
+ * and the summation tree of pico_tree/internal/align.hpp; dim != 3 or another metric than metric_l2_squared is
+ * PTK_ERR_INVALID; the deep stack class included) */
+int ptk_host_align_step(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, const float* transform,
+                        float max_distance, const float* target_normals, ptk_align_sums* out, ptk_neighbor* rows);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 

@@ -31,7 +31,8 @@ import numpy as np
 from . import datasets  # noqa: F401  (re-export)
 
 __all__ = ["KdTree", "KdForest", "save_kd_tree", "load_kd_tree", "Metric", "NEIGHBOR", "NEIGHBOR64", "FRAME", "MOMENTS", "DArray", "DeviceNeighbors", "PtkError",
-           "library_path", "device_count", "datasets", "trim_pinned_pool", "registered", "empty_pinned"]
+           "library_path", "device_count", "datasets", "trim_pinned_pool", "registered", "empty_pinned",
+           "ALIGN_SUMS", "AlignSums", "IcpResult", "icp"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: (PTK_LIBRARY: another build of the same library -- the experiment builds of tools/)
@@ -45,6 +46,11 @@ MOMENTS = np.dtype([("sum", "<f4", (3,)), ("count", "<u4"), ("outer", "<f4", (6,
 #: PTK_AGG_* (ptk.h): the ops of KdTree.aggregate_within_self / aggregate_within
 PTK_AGG_SUM, PTK_AGG_MIN, PTK_AGG_MAX, PTK_AGG_INCLUDE_SELF = 0, 1, 2, 0x100
 _AGGREGATE_OPS = {"sum": PTK_AGG_SUM, "min": PTK_AGG_MIN, "max": PTK_AGG_MAX}
+#: ptk_align_sums (ptk.h): the record of KdTree.align_step, 384 bytes
+ALIGN_SUMS = np.dtype([("count", "<u8"), ("rows", "<u8"), ("sum_distance", "<f8"), ("sum_q", "<f8", (3,)),
+                       ("sum_p", "<f8", (3,)), ("sum_qp", "<f8", (9,)), ("sum_qq", "<f8"), ("sum_pp", "<f8"),
+                       ("jtj", "<f8", (21,)), ("jtr", "<f8", (6,)), ("sum_rr", "<f8")])
+assert ALIGN_SUMS.itemsize == 384
 #: The same record of a tree over float64 points: ``neighbor<int, double>`` is 16 bytes with the
 #: distance at offset 8, which is what the reference binding's PYBIND11_NUMPY_DTYPE yields for it
 #: (_pyco_tree/def_core.hpp:17-18).
@@ -116,6 +122,11 @@ _SIGNATURES = {
                                      c_void_p]),
     "ptk_aggregate_within_device": (c_int, [c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32, c_uint32,
                                             c_void_p, c_void_p, c_void_p]),
+    "ptk_align_step_workspace": (c_int, [c_void_p, c_uint64, POINTER(c_uint64)]),
+    "ptk_align_step_device": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_uint64, c_void_p]),
+    "ptk_align_step": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "ptk_host_align_step": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -1414,6 +1425,97 @@ class KdTree:
             out = out.reshape(nq)
         return (out, cnt) if counts else out
 
+    @staticmethod
+    def _align_transform(transform):
+        """None, or the pose as 12 contiguous float32 values, row-major [R|t]: from a (3, 4) or (4, 4) matrix or 12 values."""
+        if transform is None:
+            return None
+        m = np.asarray(transform)
+        if m.shape == (4, 4):
+            m = m[:3, :]
+        if m.shape not in ((3, 4), (12,)):
+            raise ValueError(f"transform must be a (3, 4) or (4, 4) matrix or 12 values, not {m.shape}")
+        return np.ascontiguousarray(m, dtype=np.float32).reshape(12)
+
+    def align_step(self, pts, transform=None, max_distance=np.inf, normals=None, rows: bool = False,
+                   host_loop: bool = False):
+        """``align_step(pts, transform=None, max_distance=inf, normals=None, rows=False)`` -- the normal equations of one
+        ICP iteration, reduced on the device.
+
+        The source points ``pts`` are posed by ``transform`` (a (3, 4) or (4, 4) matrix ``[R|t]``, applied in float32;
+        ``None``: as they are), matched to their nearest tree point (``search_knn(q', 1)``), rejected where the squared
+        distance is not below ``max_distance``, and the sums of the accepted rows are returned as an :class:`AlignSums`
+        (``ptk_align_step``: the exact terms and the fixed order of the sums are in ``ptk.h``; every form gives the same
+        bytes).  Without ``normals`` the sums are those of point-to-point alignment; with ``normals`` -- float32
+        ``(npts, 3)`` by original point index, e.g. from :meth:`normals_within_self` -- those of point-to-plane.
+        :meth:`AlignSums.solve` turns them into the rigid increment.  ``pts`` is never rewritten.  With ``rows=True``
+        returns ``(sums, rows)``, ``rows`` being the unfiltered result of the search.  Host ``pts`` take host
+        ``normals``; a contiguous CUDA ``pts`` tensor takes a CUDA ``normals`` tensor on the same device, is enqueued on
+        the current torch stream (the workspace is the wrapper's) and the record is read when a field is first looked
+        at.  ``host_loop=True`` runs the library's host loop instead (``ptk_host_align_step``: no device needed).
+        float32 trees with three dimensions under ``Metric.L2Squared``."""
+        self._float32_only("align_step")
+        m = self._align_transform(transform)
+        mp = m.ctypes.data if m is not None else None
+        md = np.float32(max_distance)
+        lib = _load()
+        if _is_torch(pts):
+            import torch
+            if host_loop:
+                raise ValueError("host_loop=True takes host arrays")
+            if pts.dtype != torch.float32 or pts.dim() != 2 or pts.shape[1] != self._sdim:
+                raise ValueError("queries must be a float32 (nq, sdim) tensor")
+            if not pts.is_cuda or not pts.is_contiguous():
+                raise ValueError("queries must be a contiguous CUDA tensor")
+            nq = pts.shape[0]
+            if normals is not None:
+                if not (_is_torch(normals) and normals.is_cuda and normals.device == pts.device):
+                    raise ValueError(f"normals must be a CUDA tensor on {pts.device} for a device call")
+                if normals.dtype != torch.float32 or tuple(normals.shape) != (self._npts, 3) or not normals.is_contiguous():
+                    raise ValueError(f"normals must be a contiguous float32 ({self._npts}, 3) tensor")
+            need = c_uint64()
+            _check(lib.ptk_align_step_workspace(self._h, nq, byref(need)))
+            stream = torch.cuda.current_stream(pts.device)
+            # (a workspace per stream: calls on two streams must not share their temporaries)
+            cache = self.__dict__.setdefault("_align_ws", {})
+            key = (pts.device.index, stream.cuda_stream)
+            ws = cache.get(key)
+            if ws is None or ws.numel() < need.value:
+                ws = cache[key] = torch.empty((max(int(need.value), 256),), dtype=torch.uint8, device=pts.device)
+            out = torch.empty((ALIGN_SUMS.itemsize,), dtype=torch.uint8, device=pts.device)
+            raw = torch.empty((nq, 1, 2), dtype=torch.int32, device=pts.device) if rows else None
+            _check(lib.ptk_align_step_device(self._h, pts.data_ptr(), nq, mp, md,
+                                             normals.data_ptr() if normals is not None else None, out.data_ptr(),
+                                             raw.data_ptr() if rows else None, ws.data_ptr(), ws.numel(),
+                                             stream.cuda_stream))
+            done = torch.cuda.Event()
+            done.record(stream)
+            sums = AlignSums(None, normals is not None, _pending=(out, done))
+            return (sums, DeviceNeighbors(raw)) if rows else sums
+        q = self._as_matrix(pts, self._sdim, "pts", self._dtype)
+        nq = q.shape[0]
+        if normals is not None:
+            if _is_torch(normals):
+                if normals.is_cuda:
+                    raise ValueError("normals: a host call takes a host array, not a CUDA tensor")
+                normals = normals.numpy()
+            normals = np.asarray(normals)
+            if normals.dtype != np.float32 or normals.shape != (self._npts, 3):
+                raise ValueError(f"normals must be a float32 ({self._npts}, 3) array")
+            normals = np.ascontiguousarray(normals)
+        np_ = normals.ctypes.data if normals is not None else None
+        rec = np.zeros((1,), dtype=ALIGN_SUMS)
+        found = np.zeros((nq,), dtype=NEIGHBOR) if rows else None
+        fp = found.ctypes.data if rows else None
+        if host_loop:
+            _check(lib.ptk_host_align_step(self._h, self._pts.ctypes.data, q.ctypes.data, nq, mp, md, np_, rec.ctypes.data, fp))
+        else:
+            self._served(lib.ptk_align_step(self._h, q.ctypes.data, nq, mp, md, np_, rec.ctypes.data, fp),
+                         lambda lib: lib.ptk_host_align_step(self._h, self._pts.ctypes.data, q.ctypes.data, nq, mp, md, np_,
+                                                             rec.ctypes.data, fp))
+        sums = AlignSums(rec, normals is not None)
+        return (sums, found) if rows else sums
+
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""
         if _is_torch(radii):
@@ -1810,6 +1912,138 @@ class KdForest:
             self.close()
         except Exception:
             pass
+
+
+# ---- registration: the sums of KdTree.align_step and the loop around them ------------------------
+class AlignSums:
+    """The record of :meth:`KdTree.align_step` (``ptk_align_sums``): ``count``, ``rows``, ``sum_distance`` and the sums of
+    the mode -- ``sum_q``, ``sum_p``, ``sum_qp`` (3 x 3), ``sum_qq``, ``sum_pp`` for point-to-point, ``jtj`` (the 21
+    entries of the upper triangle), ``jtr``, ``sum_rr`` for point-to-plane -- as float64.  ``record`` is the 384-byte
+    numpy record itself (``tobytes()`` compares two results bit for bit)."""
+
+    def __init__(self, record, plane: bool, _pending=None):
+        self._record = record
+        self._pending = _pending
+        self.plane = bool(plane)
+
+    @property
+    def record(self) -> np.ndarray:
+        if self._record is None:  # a device call: wait for it, bring the 384 bytes down
+            out, done = self._pending
+            done.synchronize()
+            self._record = np.ascontiguousarray(out.cpu().numpy()).view(ALIGN_SUMS)
+            self._pending = None
+        return self._record
+
+    def tobytes(self) -> bytes:
+        return self.record.tobytes()
+
+    def __getattr__(self, name):
+        if name in ALIGN_SUMS.names:
+            v = self.record[name][0]
+            if name in ("count", "rows"):
+                return int(v)
+            if name == "sum_qp":
+                return v.reshape(3, 3)
+            return float(v) if v.ndim == 0 else v
+        raise AttributeError(name)
+
+    def __repr__(self) -> str:
+        return f"AlignSums({'point-to-plane' if self.plane else 'point-to-point'}, count={self.count}, rows={self.rows})"
+
+    @property
+    def normal_matrix(self) -> np.ndarray:
+        """The symmetric 6 x 6 matrix J^T J of the point-to-plane sums."""
+        a = np.zeros((6, 6))
+        a[np.triu_indices(6)] = self.jtj
+        return a + np.triu(a, 1).T
+
+    @property
+    def rms(self) -> float:
+        """Root mean square of what the mode minimises over the accepted rows: the point distance (the square root of the
+        mean squared distance) for point-to-point, the distance to the tangent plane for point-to-plane; NaN when no
+        row was accepted."""
+        if self.count == 0:
+            return float("nan")
+        return float(np.sqrt((self.sum_rr if self.plane else self.sum_distance) / self.count))
+
+    def solve(self) -> np.ndarray:
+        """The rigid increment as a 4 x 4 float64 matrix: applied AFTER the pose the sums were taken at.  Point-to-point:
+        Kabsch -- H = sum_qp - sum_q sum_p^T / count, its SVD with the determinant fix, t = mean_p - R mean_q.
+        Point-to-plane: jtj x = -jtr, the exponential map of the rotation part.  Raises below 3 (6) accepted rows."""
+        need = 6 if self.plane else 3
+        if self.count < need:
+            raise ValueError(f"align_step accepted {self.count} rows; the {'point-to-plane' if self.plane else 'point-to-point'} "
+                             f"solve needs at least {need}")
+        return solve_align_sums(self.record[0], self.plane)
+
+
+def solve_align_sums(rec, plane: bool) -> np.ndarray:
+    """:meth:`AlignSums.solve` on anything with the fields of :data:`ALIGN_SUMS` (the tests hand in exact sums)."""
+    inc = np.eye(4)
+    if plane:
+        a = np.zeros((6, 6))
+        a[np.triu_indices(6)] = np.asarray(rec["jtj"], dtype=np.float64)
+        a = a + np.triu(a, 1).T
+        x = np.linalg.solve(a, -np.asarray(rec["jtr"], dtype=np.float64))
+        w, angle = x[:3], float(np.linalg.norm(x[:3]))
+        k = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+        if angle < 1e-12:
+            rot = np.eye(3) + k
+        else:  # Rodrigues
+            rot = np.eye(3) + (np.sin(angle) / angle) * k + ((1.0 - np.cos(angle)) / (angle * angle)) * (k @ k)
+        inc[:3, :3], inc[:3, 3] = rot, x[3:]
+        return inc
+    n = float(rec["count"])
+    sq, sp = np.asarray(rec["sum_q"], dtype=np.float64), np.asarray(rec["sum_p"], dtype=np.float64)
+    h = np.asarray(rec["sum_qp"], dtype=np.float64).reshape(3, 3) - np.outer(sq, sp) / n
+    u, _, vt = np.linalg.svd(h)
+    d = np.sign(np.linalg.det(vt.T @ u.T))
+    rot = vt.T @ np.diag([1.0, 1.0, d if d != 0 else 1.0]) @ u.T
+    inc[:3, :3], inc[:3, 3] = rot, sp / n - rot @ (sq / n)
+    return inc
+
+
+class IcpResult:
+    """What :func:`icp` returns: ``transform`` (4 x 4 float64, source -> target), ``poses`` (the pose after every
+    iteration), ``rms`` (of every iteration's sums, taken BEFORE its increment), ``sums`` (the last :class:`AlignSums`),
+    ``converged``."""
+
+    def __init__(self, transform, poses, rms, sums, converged):
+        self.transform, self.poses, self.rms, self.sums, self.converged = transform, poses, rms, sums, converged
+
+    @property
+    def iterations(self) -> int:
+        return len(self.poses)
+
+
+def icp(tree: KdTree, source, max_distance, normals=None, init=None, iterations: int = 30, min_delta: float = 1e-9,
+        step=None) -> IcpResult:
+    """Iterative closest point of ``source`` against the points of ``tree``: ``iterations`` times at most,
+    :meth:`KdTree.align_step` at the current pose and the increment of :meth:`AlignSums.solve`.
+
+    The pose is composed in float64 on the host; each call receives it rounded to float32 and ``source`` is never
+    rewritten.  ``init``: the starting pose, a (4, 4) matrix (identity by default).  The loop ends early when no entry
+    of an increment differs from the identity by ``min_delta`` or more.  ``normals``: the target's normals for
+    point-to-plane steps.  ``step(pose32)`` -- ``pose32`` the (3, 4) float32 pose -- may replace the call that returns
+    the :class:`AlignSums` of an iteration (the tests drive the loop through the library's host loop with it)."""
+    pose = np.eye(4) if init is None else np.array(init, dtype=np.float64)
+    if pose.shape != (4, 4):
+        raise ValueError("init must be a (4, 4) matrix")
+    if step is None:
+        def step(pose32):
+            return tree.align_step(source, pose32, max_distance, normals)
+    poses, rms, sums, converged = [], [], None, False
+    for _ in range(int(iterations)):
+        sums = step(np.ascontiguousarray(pose[:3, :], dtype=np.float32))
+        rms.append(sums.rms)
+        inc = sums.solve()
+        pose = inc @ pose
+        poses.append(pose.copy())
+        if np.max(np.abs(inc - np.eye(4))) < min_delta:
+            converged = True
+            break
+    return IcpResult(pose, poses, rms, sums, converged)
 
 
 # ---- file I/O (the reference's PKD container, _pyco_tree/kd_tree.hpp:546-614) -------------------

@@ -298,6 +298,7 @@ struct ProcessWarmup {
       ptkf::warm_count();
       ptkf::warm_f64();
       ptkf::warm_self();
+      ptkf::warm_align();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
     });
@@ -1275,6 +1276,7 @@ void ptk_tree_destroy(ptk_tree* t) {
     if (t->d_pile_of_point) (void)hipFree(t->d_pile_of_point);
     if (t->d_pile_recs) (void)hipFree(t->d_pile_recs);
     if (t->d_count_table) (void)hipFree(t->d_count_table);
+    if (t->d_align_inverse) (void)hipFree(t->d_align_inverse);
   }
   delete t;
 }
@@ -2602,6 +2604,105 @@ int ptk_aggregate_within(const ptk_tree* t, const float* q, uint64_t nq, float r
     return ptk_aggregate_within_device(t, in.at<float>(d_in, 1), nq, radius, in.at<float>(d_in, 2), in.at<float>(d_in, 0),
                                        channels, op, res.at<float>(d_out, 0), res.at<uint64_t>(d_out, 1), s);
   });
+}
+
+// ---- align_step (ptk.h; the kernels: ptk_kernels_align.hpp) --------------------------------------------------
+
+// The inverse of the leaf permutation: built once per handle, on the first align_step, under the handle's own lock (as
+// count_table_of).
+static int align_inverse_of(const ptk_tree* t, hipStream_t s) {
+  std::lock_guard<std::mutex> lock(t->align_inverse_mutex);
+  if (t->align_inverse_built) return PTK_OK;
+  void* table = nullptr;
+  const int rc = ptkf::align_inverse(t, &table, s);
+  if (rc != PTK_OK) return rc;
+  ptk_tree* m = const_cast<ptk_tree*>(t);
+  m->d_align_inverse = table;
+  m->device_bytes += t->n_points * sizeof(uint32_t);
+  m->align_inverse_built = true;
+  return PTK_OK;
+}
+
+int ptk_align_step_workspace(const ptk_tree* t, uint64_t nq, uint64_t* bytes) {
+  if (t == nullptr || bytes == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  *bytes = ptkf::align_layout(nq).bytes;
+  return PTK_OK;
+}
+
+// Enqueues the pose kernel, the k = 1 search of q' (ptk_search_knn_device: its pieces, its batch order, its scratch) and
+// the levels of the summation tree.  Nothing is allocated and nothing waited for once the handle has its inverse
+// permutation.  The radius capture is neither read nor invalidated (a k-NN search never touches it).
+int ptk_align_step_device(const ptk_tree* t, const float* d_q, uint64_t nq, const float* transform, float max_distance,
+                          const float* d_normals, ptk_align_sums* d_out, ptk_neighbor* d_rows, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream) {
+  int rc = check_align_step(t, d_q, nq, max_distance, d_out);
+  if (rc == PTK_OK) rc = check_search(t, d_q, nq);
+  if (rc != PTK_OK) return rc;
+  const ptkf::AlignLayout w = ptkf::align_layout(nq);
+  if (nq > 0 && d_workspace == nullptr) return fail(PTK_ERR_INVALID, "align_step: null workspace");
+  if (workspace_bytes < w.bytes)
+    return fail(PTK_ERR_INVALID, "align_step: the workspace holds %llu bytes, %llu rows need %llu (ptk_align_step_workspace)",
+                (unsigned long long)workspace_bytes, (unsigned long long)nq, (unsigned long long)w.bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  if (nq == 0) return ptkf::align_reduce(t, nullptr, nullptr, 0, d_normals, max_distance, nullptr, d_out, s);
+  rc = align_inverse_of(t, s);
+  if (rc != PTK_OK) return rc;
+  char* ws = static_cast<char*>(d_workspace);
+  const float* d_qp = d_q;
+  if (transform != nullptr) {
+    rc = ptkf::align_pose(t, d_q, nq, transform, reinterpret_cast<float*>(ws + w.q), s);
+    if (rc != PTK_OK) return rc;
+    d_qp = reinterpret_cast<const float*>(ws + w.q);
+  }
+  ptk_neighbor* rows = d_rows != nullptr ? d_rows : reinterpret_cast<ptk_neighbor*>(ws + w.rows);
+  rc = ptk_search_knn_device(t, d_qp, nq, 1, 1.0f, rows, stream);
+  if (rc != PTK_OK) return rc;
+  return ptkf::align_reduce(t, reinterpret_cast<const ptk::Neighbor*>(rows), d_qp, nq, d_normals, max_distance,
+                            ws + w.partials, d_out, s);
+}
+
+// The host-buffer form: the queries and the normals go up in the handle's input block (each part on a 256-byte
+// boundary); the record, the rows and the workspace live in its output block; the record and, if asked, the rows come down.
+int ptk_align_step(const ptk_tree* t, const float* q, uint64_t nq, const float* transform, float max_distance,
+                   const float* normals, ptk_align_sums* out, ptk_neighbor* rows) {
+  int rc = check_align_step(t, q, nq, max_distance, out);
+  if (rc == PTK_OK) rc = check_search(t, q, nq);
+  if (rc != PTK_OK) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t q_bytes = (size_t)nq * 3 * sizeof(float);
+  const size_t normal_bytes = normals != nullptr && nq > 0 ? (size_t)t->n_points * 3 * sizeof(float) : 0;
+  const size_t row_bytes = (size_t)nq * sizeof(ptk_neighbor);
+  const ptkf::AlignLayout w = ptkf::align_layout(nq);
+  HostIo& io = t->io;
+  std::lock_guard<std::mutex> lock(io.mutex);
+  if (io.search[0] == nullptr) PTK_HIP(hipStreamCreateWithFlags(&io.search[0], hipStreamNonBlocking));
+  hipStream_t s = io.search[0];
+  rc = grow_device_block(&io.d_in, &io.in_capacity, pad(q_bytes) + pad(normal_bytes) + 256);
+  if (rc == PTK_OK) rc = grow_device_block(&io.d_out, &io.out_capacity, pad(sizeof(ptk_align_sums)) + pad(row_bytes) + w.bytes);
+  if (rc != PTK_OK) return rc;
+  char* d_q = io.d_in;
+  char* d_normals = d_q + pad(q_bytes);
+  auto* d_out = reinterpret_cast<ptk_align_sums*>(io.d_out);
+  auto* d_rows = reinterpret_cast<ptk_neighbor*>(io.d_out + pad(sizeof(ptk_align_sums)));
+  char* d_ws = io.d_out + pad(sizeof(ptk_align_sums)) + pad(row_bytes);
+  if (q_bytes > 0) PTK_HIP(hipMemcpyAsync(d_q, q, q_bytes, hipMemcpyHostToDevice, s));
+  if (normal_bytes > 0) PTK_HIP(hipMemcpyAsync(d_normals, normals, normal_bytes, hipMemcpyHostToDevice, s));
+  // (an empty batch reads no normals: only the mode is taken from the pointer)
+  rc = ptk_align_step_device(t, reinterpret_cast<const float*>(d_q), nq, transform, max_distance,
+                             normals != nullptr ? reinterpret_cast<const float*>(d_normals) : nullptr, d_out, d_rows, d_ws,
+                             w.bytes, s);
+  if (rc != PTK_OK) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  PTK_HIP(hipMemcpyAsync(out, d_out, sizeof(ptk_align_sums), hipMemcpyDeviceToHost, s));
+  if (rows != nullptr && nq > 0) PTK_HIP(hipMemcpyAsync(rows, d_rows, row_bytes, hipMemcpyDeviceToHost, s));
+  PTK_HIP(hipStreamSynchronize(s));
+  return PTK_OK;
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 //   ptk_family_f64.hip     double precision (ptk_backend_f64.hpp)
 //   ptk_family_self.hip    search_knn_self: the direct kernel over the tree's own records, the staged route's two kernels;
 //                          search_radius_self / count_within_self (ptk_kernels_selfr.hpp), float32 and float64
+//   ptk_family_align.hip   align_step (ptk_kernels_align.hpp): the pose, the inverse leaf permutation, the summation tree
 // Everything here is `inline` (or a type): every unit sees the same definitions, the linker keeps one.
 #pragma once
 
@@ -257,6 +258,11 @@ struct ptk_tree {
   void* d_count_table = nullptr;
   bool count_table_built = false;
   mutable std::mutex count_table_mutex;
+  // align_step (ptk_kernels_align.hpp): the inverse of the leaf permutation, uint32 per point, built on the first call
+  // and kept.
+  void* d_align_inverse = nullptr;
+  bool align_inverse_built = false;
+  mutable std::mutex align_inverse_mutex;
 
   std::atomic<int> reorder{PTK_REORDER_AUTO};
   std::atomic<int> metric{PTK_METRIC_L2_SQUARED};
@@ -810,6 +816,19 @@ inline int check_aggregate_within(const ptk_tree* t, const void* q, uint64_t nq,
     return fail(PTK_ERR_UNSUPPORTED, "aggregate_within: %s (ptk_host_aggregate_within)", why.c_str());
   }
   return rc;
+}
+
+// align_step (ptk.h): a rigid motion is Euclidean 3-D -- dim != 3 and every metric but metric_l2_squared are
+// PTK_ERR_INVALID from every form, the host loop included; then the arguments of its own.
+inline int check_align_step(const ptk_tree* t, const void* q, uint64_t nq, float max_distance, const void* out) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  if (t->dim != 3) return fail(PTK_ERR_INVALID, "align_step: a rigid motion is defined for 3-D points, not dim %u", t->dim);
+  if (t->metric.load() != PTK_METRIC_L2_SQUARED)
+    return fail(PTK_ERR_INVALID, "align_step: the sums are those of metric_l2_squared, not of the handle's metric");
+  if (!(max_distance >= 0.0f)) return fail(PTK_ERR_INVALID, "align_step: max_distance must be >= 0 (and not NaN)");
+  if (out == nullptr) return fail(PTK_ERR_INVALID, "align_step: null output record");
+  if (nq > 0 && q == nullptr) return fail(PTK_ERR_INVALID, "null query buffer");
+  return PTK_OK;
 }
 
 // cluster_within_self (ptk.h): n_clusters of the host forms -- the labels that name their own entry.

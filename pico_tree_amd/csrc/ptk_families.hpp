@@ -179,6 +179,23 @@ int frames_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, con
 int aggregate_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, const float* d_values,
                    uint32_t channels, uint32_t flags, float* d_out, uint64_t* d_counts, hipStream_t s);
 void warm_self();
+// ptk_family_align.hip: align_step (ptk_kernels_align.hpp).  The caller's workspace holds q', the rows
+// (used when the caller keeps none) and the partials of every level: per entry of a level the 29 sums of the wider mode
+// and a count.
+constexpr size_t kAlignEntryBytes = 30 * 8;
+struct AlignLayout {
+  size_t q, rows, partials, bytes;  // offsets of the three parts (256-byte aligned), the size of the whole
+};
+AlignLayout align_layout(uint64_t nq);
+// The handle's inverse leaf permutation (uint32 per point): allocated, filled by one scatter kernel on `s`, waited for.
+int align_inverse(const ptk_tree* t, void** d_inv, hipStream_t s);
+// d_out[i] = R q_i + t; `m`: 12 host floats, row-major [R|t]
+int align_pose(const ptk_tree* t, const float* d_q, uint64_t nq, const float* m, float* d_out, hipStream_t s);
+// The levels of the summation tree over the rows of the k = 1 search of d_qp, and the record; d_normals null:
+// point-to-point.  Reads the handle's inverse permutation (built before: align_inverse_of).
+int align_reduce(const ptk_tree* t, const ptk::Neighbor* d_rows, const float* d_qp, uint64_t nq, const float* d_normals,
+                 float max_distance, char* d_partials, ptk_align_sums* d_out, hipStream_t s);
+void warm_align();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.
 constexpr size_t kSelfStageBytes = size_t(256) << 20;

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "pico_tree/internal/aggregate.hpp"
+#include "pico_tree/internal/align.hpp"
 #include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
 #include "pico_tree/internal/local_frame.hpp"
@@ -583,6 +584,43 @@ int ptk_host_aggregate_within(const ptk_tree* t, const float* points, const floa
       internal::aggregate_row(values, channels, kind, nullptr, row, out + i * channels);
       if (counts != nullptr) counts[i] = row.size();
     });
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// align_step (ptk.h) as the contract reads: the pose on the host, the rows of ptk_host_search_knn above with k = 1 and
+// e = 1, then the terms and the summation tree of pico_tree/internal/align.hpp, a block of 256 rows at a time.
+int ptk_host_align_step(const ptk_tree* t, const float* points, const float* q, uint64_t nq, const float* transform,
+                        float max_distance, const float* normals, ptk_align_sums* out, ptk_neighbor* rows) {
+  int rc = check_align_step(t, q, nq, max_distance, out);
+  if (rc != PTK_OK) return rc;
+  if (points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  try {
+    using namespace ptk_host;
+    std::vector<float> posed;
+    const float* qp = q;
+    if (transform != nullptr && nq > 0) {
+      posed.resize((size_t)nq * 3);
+      rows_loop(nq, [&](uint64_t i) { internal::align_pose(transform, q[3 * i], q[3 * i + 1], q[3 * i + 2], &posed[3 * i]); });
+      qp = posed.data();
+    }
+    std::vector<ptk_neighbor> own;
+    if (rows == nullptr && nq > 0) {
+      own.resize((size_t)nq);
+      rows = own.data();
+    }
+    rc = ptk_host_search_knn(t, points, qp, nq, 1, 1.0f, rows);
+    if (rc != PTK_OK) return rc;
+    const ptk_neighbor* found = rows;
+    internal::align_reduce_rows(
+        qp, nq, [&](uint64_t i, int32_t& index, float& distance) { index = found[i].index, distance = found[i].distance; },
+        [&](int32_t index) { return points + 3 * (size_t)index; }, normals, max_distance,
+        [](uint64_t n, auto&& f) { rows_loop(n, f); },
+        reinterpret_cast<internal::align_sums*>(out));
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
   } catch (const std::exception& ex) {
