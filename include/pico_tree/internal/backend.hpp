@@ -234,6 +234,9 @@ struct ptk_api<float> {
                               std::uint64_t* counts) {
     return ptk_aggregate_within(t, q, nq, radius, radii, values, channels, op, out, counts);
   }
+  static int suppress_within_self(tree const* t, float radius, float const* radii, float const* scores, std::uint8_t* keep) {
+    return ptk_suppress_within_self(t, radius, radii, scores, keep, nullptr, nullptr);
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }
@@ -280,6 +283,9 @@ struct ptk_api<double> {
   }
   static int cluster_within_self(tree const* t, double radius, double const* radii, std::uint64_t min_neighbors, std::int32_t* labels) {
     return ptk_search64_cluster_within_self(t, radius, radii, min_neighbors, labels, nullptr);
+  }
+  static int suppress_within_self(tree const* t, double radius, double const* radii, float const* scores, std::uint8_t* keep) {
+    return ptk_search64_suppress_within_self(t, radius, radii, scores, keep, nullptr, nullptr);
   }
   static int radius_self(tree const* t, double radius, double const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search64_radius_self(t, radius, radii, sort, offsets, out);

@@ -39,6 +39,7 @@
 #include "internal/flat_tree.hpp"
 #include "internal/local_frame.hpp"
 #include "internal/stream.hpp"
+#include "internal/suppress.hpp"
 #include "internal/visitors.hpp"
 #include "metric.hpp"
 
@@ -439,6 +440,27 @@ class kd_tree {
       std::vector<scalar_type> const& radii, std::int32_t* labels, size_type const min_neighbors = 0) const {
     check_radii(radii, view().size());
     batched_cluster_within_self(scalar_type(0), radii.data(), labels, min_neighbors);
+  }
+
+  //! Greedy radius suppression of the tree's points: thinning to an r-separated
+  //! subset, or non-maximum suppression under \p scores.  With row i being
+  //! search_radius_self's row i and key(i) = (ord_i << 32) | (0xFFFFFFFF - i)
+  //! -- ord_i the total-order map of the bits of scores[i], or fmix32(i) when
+  //! \p scores is null (internal/suppress.hpp) -- keep[i] = 1 iff row i holds
+  //! no j with key(j) > key(i) and keep[j] == 1, else 0: the greedy pass in
+  //! descending key.  keep: size() entries; scores: null or size() float
+  //! entries, none NaN (std::invalid_argument).  Served by the backend
+  //! (ptk_suppress_within_self); where it refuses (and allow_host_loop is on),
+  //! and in a build with PICO_TREE_HOST_ONLY defined, by the per-point member
+  //! plus the greedy pass.
+  inline void suppress_within_self(scalar_type const radius, std::uint8_t* keep, float const* scores = nullptr) const {
+    batched_suppress_within_self(radius, nullptr, scores, keep);
+  }
+
+  inline void suppress_within_self(
+      std::vector<scalar_type> const& radii, std::uint8_t* keep, float const* scores = nullptr) const {
+    check_radii(radii, view().size());
+    batched_suppress_within_self(scalar_type(0), radii.data(), scores, keep);
   }
 
   //! PCA normals and curvature of the tree's points (float points, three
@@ -997,6 +1019,33 @@ class kd_tree {
       internal::ptk_check(
           api::cluster_within_self(device(), radius, radii, static_cast<std::uint64_t>(min_neighbors), labels),
           "ptk_cluster_within_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  void batched_suppress_within_self(
+      scalar_type radius, scalar_type const* radii, float const* scores, std::uint8_t* keep) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    size_type const n = view().size();
+    if (scores != nullptr && internal::suppress_first_nan(scores, n) != n) {
+      throw std::invalid_argument("pico_tree: scores must not hold a NaN");
+    }
+    auto const rows_loop = [&]() {
+      std::vector<std::vector<neighbor_type>> rows(n);
+      internal::host_rows_loop(n, [&](size_type i) {
+        search_radius_self(static_cast<index_type>(i), radii != nullptr ? radii[i] : radius, rows[i]);
+      });
+      internal::suppress_rows(rows, scores, keep);
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(api::suppress_within_self(device(), radius, radii, scores, keep), "ptk_suppress_within_self");
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

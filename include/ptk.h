@@ -483,6 +483,63 @@ int ptk_cluster_within_self(const ptk_tree* tree, float radius, const float* rad
 int ptk_cluster_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, uint64_t min_neighbors,
                                    int32_t* d_labels, void* stream);
 
+/* ---- suppress_within_self: greedy radius suppression of a tree's own points ------------------------------------------
+ * Thins the tree's points to an r-separated subset (Poisson-disk / "spatial" subsampling) or, with scores, keeps the
+ * points whose score is a local maximum within r (greedy non-maximum suppression).  No rows are written: a traversal of
+ * each point's own radius row looks at one cell per hit, in rounds, on the device.
+ *   Inputs.  `radius`, or `radii` (n_points entries by ORIGINAL point index; non-NULL: `radius` is ignored), as
+ * ptk_search_count_within_self takes them.  Let row i be row i of ptk_search_radius_self on the same handle with the same
+ * radius or radii: the other points j with distance(i, j) < radius_i (exact, strict <, the handle's metric and its unit:
+ * squared under metric_l2_squared, the own entry removed).  `scores`: NULL, or n_points float32 entries by original
+ * point index (float32 for float64 trees too: the key has 32 bits for them).
+ *   Keys.  key(i) = ((uint64_t)ord_i << 32) | (0xFFFFFFFF - i).  With scores, ord_i is the total-order map of the bits b
+ * of scores[i]: b ^ 0xFFFFFFFF if the sign bit of b is set, else b ^ 0x80000000 -- a higher score gives a higher key, an
+ * equal score is decided by the LOWER index, -0.0 lies below +0.0, +-inf are ordinary values.  With scores == NULL,
+ * ord_i = fmix32(i), the 32-bit finaliser
+ *     h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16;
+ * a bijection of the 32-bit integers: the order is a fixed pseudo-random permutation of the indices.  Keys are distinct
+ * in both cases.  (Why hashed and not the index order: the rounds below need a dozen rounds in a hashed order on any
+ * cloud measured, and hundreds in index order on a cloud sorted along an axis -- which is how a LiDAR scan arrives.)
+ *   Result.  keep (uint8, n_points entries by original point index): keep[i] = 1 iff row i holds no j with
+ * key(j) > key(i) and keep[j] == 1; else 0.  This is well-founded by descending key -- it is the greedy pass over the
+ * points in key order -- and reads only the point's OWN row, so it stays defined for per-point radii and for rows that
+ * are not symmetric.  Nothing depends on launch order, lane order or the number of pieces: two calls give identical
+ * arrays.  n_kept (host forms; may be NULL) is the number of i with keep[i] == 1.  What follows:
+ *   - Separation.  With a scalar radius under metric_l2_squared or metric_l1 the kept set is a maximal r-separated
+ *     subset: no two kept points are closer than r, and every suppressed point has a kept one closer than r.
+ *   - Piles.  Of a pile of coincident points exactly one is kept, for any r > 0: the one of highest key.  (Precisely:
+ *     at most one, and exactly one unless a kept point OUTSIDE the pile, of higher key still, lies within r of it --
+ *     that point then suppresses the whole pile.)
+ *   - Radius 0 keeps everything.
+ *   Values, as in the self radius searches.  +inf, FLT_MAX / DBL_MAX and subnormal radii are valid.  A NaN or negative
+ * scalar radius is PTK_ERR_INVALID.  A NaN or negative radii entry, or a NaN score, is PTK_ERR_INVALID in the
+ * host-buffer forms and the host loop (the message names the first such row); the _device forms cannot look: there such
+ * a radius gives an empty row -- the point is kept, and it can still suppress others through THEIR rows -- and a NaN
+ * score takes the place its bits give it under ord.  A null keep with n_points > 0 is PTK_ERR_INVALID, a host-only handle
+ * PTK_ERR_DEVICE; n_points == 0 succeeds.
+ *   Where the device serves it: exactly the handles ptk_search_count_within_self serves, refused through the same check
+ * with the same messages, naming ptk_host_suppress_within_self (every float32 handle, the topological metrics
+ * included).  There is no staged route.
+ *   Rounds.  The cells of keep hold a third state, "undecided", while the call runs.  A round walks the row of every
+ * undecided point: a kept point of higher key in it suppresses the point, an undecided one blocks it until the next
+ * round, otherwise it is kept.  The rounds end when one leaves nothing undecided.  Every round decides at least the
+ * undecided point of highest key (all cells above it were final before the launch), so there are at most n_points
+ * rounds -- reached by n collinear points at spacing 1 with radius 1.5 (squared: 2.25) whose keys descend along the line:
+ * point k waits for point k - 1.  The default order needs about a dozen.  n_rounds (may be NULL) is information only:
+ * the rounds launched; it is no part of the results contract and may differ between two calls.
+ *   State and waiting.  The handle's radius capture is neither read nor invalidated; no side table is built.  UNLIKE THE
+ * OTHER _device FORMS this one WAITS on `stream` once per round and reads 4 bytes back.  It waits on that stream only:
+ * the 4-byte counter of the call and its page-locked twin come from a pool the library keeps per device and go back to
+ * it (nothing is freed, so nothing waits for the device; the first calls on a device allocate).  It cannot be captured
+ * into a graph: a `stream` that is being captured is PTK_ERR_INVALID, by name, before anything is enqueued.  d_keep is
+ * the only working array.  The float64 form takes the handle's stack block (it grows on first use) and holds the
+ * handle's lock from its first round to its last wait: another thread's float64 search of the SAME handle stands behind
+ * the whole call, not behind one launch.  In the host form the radii and scores go up, keep comes down. */
+int ptk_suppress_within_self(const ptk_tree* tree, float radius, const float* radii, const float* scores, uint8_t* keep,
+                             uint64_t* n_kept, uint32_t* n_rounds);
+int ptk_suppress_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, const float* d_scores,
+                                    uint8_t* d_keep, uint32_t* n_rounds, void* stream);
+
 /* ---- normals_within_self: PCA normals and curvature of a tree's own points ------------------------------------------
  * The moments of each point's neighbourhood, their covariance, and the local frame of it (surface normal, curvature,
  * eigenvalues), accumulated inside the traversal of the self radius search: no rows are written.  float32 trees with
@@ -732,6 +789,10 @@ int ptk_host_aggregate_within(const ptk_tree* tree, const float* points, const f
  * PTK_ERR_INVALID; the deep stack class included) */
 int ptk_host_align_step(const ptk_tree* tree, const float* points, const float* queries, uint64_t nq, const float* transform,
                         float max_distance, const float* target_normals, ptk_align_sums* out, ptk_neighbor* rows);
+/* (ptk_suppress_within_self as the contract reads: the rows of ptk_host_search_radius_self, a sort by key, one greedy
+ * pass in descending key; every metric, the topological ones included) */
+int ptk_host_suppress_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
+                                  const float* scores, uint8_t* keep, uint64_t* n_kept);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 
@@ -850,6 +911,11 @@ int ptk_search64_cluster_within_self(const ptk_tree64* tree, double radius, cons
                                      int32_t* labels, uint64_t* n_clusters);
 int ptk_search64_cluster_within_self_device(const ptk_tree64* tree, double radius, const double* d_radii,
                                             uint64_t min_neighbors, int32_t* d_labels, void* stream);
+/* As ptk_suppress_within_self / _device: radii in double, scores in float32. */
+int ptk_search64_suppress_within_self(const ptk_tree64* tree, double radius, const double* radii, const float* scores,
+                                      uint8_t* keep, uint64_t* n_kept, uint32_t* n_rounds);
+int ptk_search64_suppress_within_self_device(const ptk_tree64* tree, double radius, const double* d_radii,
+                                             const float* d_scores, uint8_t* d_keep, uint32_t* n_rounds, void* stream);
 /* As ptk_search_box. */
 int ptk_search64_box(const ptk_tree64* tree, const double* mins,
                      const double* maxs, uint64_t nb, uint64_t* offsets,

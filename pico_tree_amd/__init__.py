@@ -127,6 +127,8 @@ _SIGNATURES = {
                                       c_uint64, c_void_p]),
     "ptk_align_step": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "ptk_host_align_step": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "ptk_suppress_within_self": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_suppress_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_search_count_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search_radius_self": (c_int, [c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -165,6 +167,7 @@ _SIGNATURES = {
                                                c_void_p]),
     "ptk_host_aggregate_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32,
                                           c_uint32, c_void_p, c_void_p]),
+    "ptk_host_suppress_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -194,6 +197,9 @@ _SIGNATURES = {
     "ptk_search64_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
     "ptk_search64_cluster_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_cluster_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_suppress_within_self": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_search64_suppress_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p]),
     "ptk_search64_count_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p]),
     "ptk_search64_count_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_radius_self": (c_int, [c_void_p, c_double, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
@@ -1515,6 +1521,104 @@ class KdTree:
                                                              rec.ctypes.data, fp))
         sums = AlignSums(rec, normals is not None)
         return (sums, found) if rows else sums
+
+    def _suppress_scores(self, scores, device):
+        """The scores of :meth:`suppress_within_self`: None, a contiguous float32 host array of ``npts`` entries without a
+        NaN, or -- ``device``: the torch device of a device call -- a contiguous float32 CUDA tensor on it, taken as it is
+        (a host array-like is checked and uploaded)."""
+        if scores is None:
+            return None
+        n = self._npts
+        if device is not None and _is_torch(scores) and scores.is_cuda:
+            import torch
+            if scores.device != device:
+                raise ValueError(f"scores must be on the tree's device ({device}), not on {scores.device}")
+            if scores.dtype != torch.float32:
+                raise ValueError(f"scores must be a float32 tensor, not {scores.dtype}")
+            if scores.dim() != 1 or scores.shape[0] != n:
+                raise ValueError(f"scores must be a 1-D tensor of {n} scores, one per tree point")
+            if not scores.is_contiguous():
+                raise ValueError("scores must be a contiguous tensor")
+            return scores
+        if _is_torch(scores):
+            if scores.is_cuda:
+                raise ValueError("scores: a host call takes a host array, not a CUDA tensor")
+            scores = scores.numpy()
+        try:
+            host = np.asarray(scores)
+            if host.dtype.kind not in "fiub":
+                raise TypeError
+            wide = host
+            with np.errstate(over="ignore"):  # (a value that does not fit is refused below)
+                host = np.ascontiguousarray(host, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"scores must be None or an array of {n} numbers") from None
+        if host.ndim != 1 or host.shape[0] != n:
+            raise ValueError(f"scores must be a 1-D array of {n} scores, one per tree point, not {tuple(host.shape)}")
+        if wide.dtype.kind == "f" and wide.dtype.itemsize > 4 and np.any(np.isinf(host) & ~np.isinf(wide)):
+            raise ValueError("scores: a value does not fit float32 (the key holds a float32 score)")
+        bad = np.flatnonzero(np.isnan(host))
+        if len(bad):
+            raise ValueError(f"scores[{int(bad[0])}] must not be NaN")
+        if device is not None:
+            import torch
+            return torch.from_numpy(host if host.flags.writeable else host.copy()).to(device)
+        return host
+
+    def suppress_within_self(self, radius, scores=None, indices: bool = False, device: bool = False):
+        """``suppress_within_self(radius, scores=None, indices=False, device=False)`` -- greedy radius suppression of the
+        tree's points: thinning to an r-separated subset (Poisson-disk / spatial subsampling), or with ``scores``
+        non-maximum suppression ("keep the points whose score is a local maximum within r").
+
+        With row i being :meth:`search_radius_self`'s row i (the other points j with ``distance(i, j) < radius_i``,
+        strict, in the metric's own unit -- squared under ``L2Squared``) and
+        ``key(i) = (ord_i << 32) | (0xFFFFFFFF - i)``: ``keep[i]`` is True iff row i holds no j with
+        ``key(j) > key(i)`` and ``keep[j]`` True -- the greedy pass over the points in descending key.  With ``scores``
+        (``npts`` float32 values by original point index, no NaN) ``ord_i`` is the total-order map of the score's bits
+        (``b ^ 0xFFFFFFFF`` if the sign bit is set, else ``b ^ 0x80000000``): a higher score wins, an equal score is
+        decided by the lower index, ``-0.0`` lies below ``+0.0``, infinities are ordinary values.  Without,
+        ``ord_i = fmix32(i)`` (the 32-bit finaliser written out in ``ptk.h``): a fixed pseudo-random order.  With a
+        scalar radius under ``L2Squared`` or ``L1`` the kept set is a maximal r-separated subset; of a pile of
+        coincident points exactly one is kept for any r > 0 (the one of highest key -- unless a kept point outside the
+        pile, of higher key still, lies within r and suppresses all of it); radius 0 keeps everything.  ``radius`` is a scalar or an
+        array of ``npts`` radii by original point index.  No rows are written (``ptk_suppress_within_self`` /
+        ``ptk_search64_suppress_within_self``).
+
+        Returns a ``bool[npts]`` array; with ``indices=True`` the kept original indices ascending (``int64``).  With
+        ``device=True`` the result is a CUDA tensor on the tree's device and the work is enqueued on the current torch
+        stream; ``scores`` may then be a contiguous float32 CUDA tensor, taken as it is (a NaN takes the place its bits
+        give it, a NaN or negative radius entry gives an empty row: the point is kept).  Unlike the other device forms
+        this call WAITS on that stream once per round (it reads a 4-byte counter back) and cannot be captured into a
+        graph (a capturing stream raises).  ``tree.last_suppress_rounds`` holds the number of rounds launched (information only).  Served where
+        :meth:`count_within_self` is; the rest is refused (``allow_host_loop`` serves float32 trees)."""
+        n = self._npts
+        lib = _load()
+        rounds = ctypes.c_uint32(0)
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            r, radii = self._self_radii(radius, True)
+            d_scores = self._suppress_scores(scores, dev)
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            fn = lib.ptk_search64_suppress_within_self_device if self._f64 else lib.ptk_suppress_within_self_device
+            _check(fn(self._h, r, radii.data_ptr() if radii is not None else None,
+                      d_scores.data_ptr() if d_scores is not None else None, out.data_ptr(), byref(rounds), stream))
+            self.last_suppress_rounds = int(rounds.value)
+            keep = out.to(torch.bool)
+            return torch.nonzero(keep).reshape(-1) if indices else keep
+        r, radii = self._self_radii(radius, False)
+        host = self._suppress_scores(scores, None)
+        keep = np.zeros((n,), dtype=np.uint8)
+        rp = radii.ctypes.data if radii is not None else None
+        sp = host.ctypes.data if host is not None else None
+        fn = lib.ptk_search64_suppress_within_self if self._f64 else lib.ptk_suppress_within_self
+        self._served(fn(self._h, r, rp, sp, keep.ctypes.data, None, byref(rounds)),
+                     lambda lib: lib.ptk_host_suppress_within_self(self._h, self._pts.ctypes.data, r, rp, sp,
+                                                                   keep.ctypes.data, None))
+        self.last_suppress_rounds = int(rounds.value)
+        keep = keep.astype(bool)
+        return np.flatnonzero(keep).astype(np.int64) if indices else keep
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

@@ -299,6 +299,7 @@ struct ProcessWarmup {
       ptkf::warm_f64();
       ptkf::warm_self();
       ptkf::warm_align();
+      ptkf::warm_suppress();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
     });
@@ -2514,6 +2515,51 @@ int ptk_cluster_within_self(const ptk_tree* t, float radius, const float* radii,
   });
   if (src == PTK_OK && n_clusters != nullptr) *n_clusters = count_cluster_roots(labels, t->n_points);
   return src;
+}
+
+// ---- suppress_within_self (ptk.h; the round: ptk_kernels_suppress.hpp) -----------------------------------
+
+// Enqueues the init kernel and then ROUNDS on `stream`, each over all pieces of leaf positions before the next, until a
+// round leaves no point undecided.  d_keep is the only working array.  Unlike the other _device forms this one WAITS on
+// the stream once per round and reads 4 bytes (a stream under capture is refused); the call's counter comes from the
+// library's pool (ptkf::SuppressCounter: nothing is freed, so nothing waits for the device).  The handle's radius
+// capture is neither read nor invalidated; no side table is read.
+int ptk_suppress_within_self_device(const ptk_tree* t, float radius, const float* d_radii, const float* d_scores,
+                                    uint8_t* d_keep, uint32_t* n_rounds, void* stream) {
+  if (n_rounds != nullptr) *n_rounds = 0;
+  const int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_keep, "suppress_within_self",
+                                   "ptk_host_suppress_within_self");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const int crc = ptkf::suppress_check_stream(s);
+  if (crc != PTK_OK) return crc;
+  return ptkf::suppress_rounds(t->n_points, d_keep, s, n_rounds, [&](uint32_t* d_undecided, bool later_round) {
+    return in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+      return ptkf::suppress_self(t, first, n, radius, d_radii, d_scores, d_keep, d_undecided, later_round, s);
+    });
+  });
+}
+
+// The host form: the radii and the scores go up, `keep` comes down; n_kept (may be null) counts the keep[i] == 1.
+int ptk_suppress_within_self(const ptk_tree* t, float radius, const float* radii, const float* scores, uint8_t* keep,
+                             uint64_t* n_kept, uint32_t* n_rounds) {
+  if (n_kept != nullptr) *n_kept = 0;
+  if (n_rounds != nullptr) *n_rounds = 0;
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, keep, "suppress_within_self",
+                             "ptk_host_suppress_within_self");
+  if (rc == PTK_OK) rc = check_scores(scores, t->n_points);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(float)),
+                        ptkio::in_part(scores, (size_t)t->n_points * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(keep, (size_t)t->n_points)};
+  rc = host_form(t, in, out, [&](char* d_in, char* d_out, hipStream_t s) {
+    return ptk_suppress_within_self_device(t, radius, in.at<float>(d_in, 0), in.at<float>(d_in, 1), out.at<uint8_t>(d_out, 0),
+                                           n_rounds, s);
+  });
+  if (rc == PTK_OK && n_kept != nullptr) *n_kept = count_kept(keep, t->n_points);
+  return rc;
 }
 
 // ---- normals_within_self (ptk.h; the kernel: ptk_kernels_frames.hpp) ----------------------------------------

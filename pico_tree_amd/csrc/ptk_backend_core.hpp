@@ -66,6 +66,7 @@ constexpr int kGenLeafB = 5;  // points per leaf round of the general searches (
 // Host-side builder: the product's own header-only flat-tree builder.
 #include "pico_tree/internal/flat_tree.hpp"
 #include "pico_tree/internal/stream.hpp"
+#include "pico_tree/internal/suppress.hpp"
 #include "pico_tree/map.hpp"
 
 
@@ -836,6 +837,19 @@ inline uint64_t count_cluster_roots(const int32_t* labels, uint64_t n) {
   uint64_t roots = 0;
   for (uint64_t i = 0; i < n; ++i) roots += labels[i] == (int32_t)i ? 1u : 0u;
   return roots;
+}
+
+// suppress_within_self (ptk.h): the scores of the host forms (null: the default order) -- a NaN has no place in the
+// order a caller means; the message names the first such row.  n_kept of the host forms -- the cells that hold 1.
+inline int check_scores(const float* scores, uint64_t n) {
+  if (scores == nullptr) return PTK_OK;
+  const uint64_t i = pico_tree::internal::suppress_first_nan(scores, n);  // (the one scan, shared with kd_tree.hpp)
+  return i == n ? PTK_OK : fail(PTK_ERR_INVALID, "scores[%llu] must not be NaN", (unsigned long long)i);
+}
+inline uint64_t count_kept(const uint8_t* keep, uint64_t n) {
+  uint64_t kept = 0;
+  for (uint64_t i = 0; i < n; ++i) kept += keep[i] == 1 ? 1u : 0u;
+  return kept;
 }
 
 inline float inv_ratio(float e) { return 1.0f / e; }

@@ -1403,6 +1403,54 @@ int ptk_search64_cluster_within_self(const ptk_tree64* t, double radius, const d
   return rc;
 }
 
+// suppress_within_self in double (the round: ptk_kernels_suppress.hpp), each round over all pieces of leaf positions
+// before the next; the record stacks of a launch live in the handle's stack block (the lease's piece, held for the whole
+// call), d_keep is the only working array.  Waits on the stream once per round, as the float32 form.
+int ptk_search64_suppress_within_self_device(const ptk_tree64* t, double radius, const double* d_radii, const float* d_scores,
+                                             uint8_t* d_keep, uint32_t* n_rounds, void* stream) {
+  if (n_rounds != nullptr) *n_rounds = 0;
+  int rc = check_radius_self(t, radius, d_radii, /*host_values=*/false, d_keep, "suppress_within_self",
+                             "kd_tree::suppress_within_self, one point at a time");
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = ptkf::suppress_check_stream(s);
+  if (rc != PTK_OK) return rc;
+  // (the lease holds the handle's lock over every round AND its wait: another thread's float64 search of this handle
+  // stands behind the whole call -- ptk.h says so)
+  Stack64Lease lease(t, s);
+  rc = lease.acquire(t->n_points);
+  if (rc != PTK_OK) return rc;
+  const uint64_t np = t->n_points;
+  return ptkf::suppress_rounds(np, d_keep, s, n_rounds, [&](uint32_t* d_undecided, bool) {
+    int prc = PTK_OK;
+    for (uint64_t first = 0; first < np && prc == PTK_OK; first += lease.piece)
+      prc = ptkf::suppress64_self(t->dev, t->metric.load(), first, std::min<uint64_t>(lease.piece, np - first), radius, d_radii,
+                                  d_scores, d_keep, d_undecided, lease.stack, t->slots, s);
+    return prc;
+  });
+}
+
+int ptk_search64_suppress_within_self(const ptk_tree64* t, double radius, const double* radii, const float* scores,
+                                      uint8_t* keep, uint64_t* n_kept, uint32_t* n_rounds) {
+  if (n_kept != nullptr) *n_kept = 0;
+  if (n_rounds != nullptr) *n_rounds = 0;
+  int rc = check_radius_self(t, radius, radii, /*host_values=*/true, keep, "suppress_within_self",
+                             "kd_tree::suppress_within_self, one point at a time");
+  if (rc == PTK_OK) rc = check_scores(scores, t->n_points);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  const ptkio::Parts in{ptkio::in_part(radii, (size_t)t->n_points * sizeof(double)),
+                        ptkio::in_part(scores, (size_t)t->n_points * sizeof(float))};
+  const ptkio::Parts out{ptkio::out_part(keep, (size_t)t->n_points)};
+  rc = host_form64(t, in, out, [&](char* d_in, char* d_out) {
+    return ptk_search64_suppress_within_self_device(t, radius, in.at<double>(d_in, 0), in.at<float>(d_in, 1),
+                                                    out.at<uint8_t>(d_out, 0), n_rounds, nullptr);
+  });
+  if (rc == PTK_OK && n_kept != nullptr) *n_kept = count_kept(keep, t->n_points);
+  return rc;
+}
+
 int ptk_search64_box(const ptk_tree64* t, const double* mins, const double* maxs, uint64_t nb, uint64_t* offsets,
                      int32_t** out) {
   if (out != nullptr) *out = nullptr;

@@ -196,6 +196,72 @@ int align_pose(const ptk_tree* t, const float* d_q, uint64_t nq, const float* m,
 int align_reduce(const ptk_tree* t, const ptk::Neighbor* d_rows, const float* d_qp, uint64_t nq, const float* d_normals,
                  float max_distance, char* d_partials, ptk_align_sums* d_out, hipStream_t s);
 void warm_align();
+// ptk_family_suppress.hip: suppress_within_self (ptk_kernels_suppress.hpp).  d_keep (n_points uint8
+// cells by original index) is the caller's output and the only working array: suppress_init sets every cell to
+// "undecided"; suppress_self / suppress64_self is ONE ROUND over leaf positions [first, first + n) of a handle
+// check_radius_self serves (d_radii null: every point gets `radius`; d_scores null: the default order) and adds the lanes
+// it leaves undecided to *d_undecided.  The caller runs a round over all pieces before the next, on one stream, until a
+// round adds nothing.  `later_round`: not the first round of its call (the profile counts it as the search's tail).
+int suppress_init(uint64_t n, uint8_t* d_keep, hipStream_t s);
+int suppress_self(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_radii, const float* d_scores,
+                  uint8_t* d_keep, uint32_t* d_undecided, bool later_round, hipStream_t s);
+int suppress64_self(const ptk::DevTree64& dev, int metric, uint64_t first, uint64_t n, double radius, const double* d_radii,
+                    const float* d_scores, uint8_t* d_keep, uint32_t* d_undecided, ptk::Rec64* stack, uint32_t slots,
+                    hipStream_t s);
+// The counter of a call: one device word, zeroed on the stream before a round, and one page-locked word it is copied to
+// after the round -- read() WAITS for the stream.  Both belong to the call while it runs (two calls on two streams share
+// nothing); they come from a pool the library keeps per device and go back to it when the call returns: nothing is
+// freed, because hipFree / hipHostFree wait for the WHOLE device, every other stream's work included.  The pool grows to
+// the largest number of calls that ever ran side by side on a device (8 bytes each) and lives as long as the process.
+struct SuppressCounter {
+  uint32_t* d_word = nullptr;
+  uint32_t* h_word = nullptr;
+  int device = -1;
+  SuppressCounter() = default;
+  SuppressCounter(const SuppressCounter&) = delete;
+  SuppressCounter& operator=(const SuppressCounter&) = delete;
+  ~SuppressCounter();  // back to the pool
+  int alloc();         // from the pool of the current device; a new pair on the first calls only
+  int zero(hipStream_t s);
+  int read(hipStream_t s, uint32_t* undecided);
+};
+// The rounds of either precision: `round(d_undecided, later_round)` enqueues one round over all pieces.  *n_rounds (may be null): the
+// rounds launched.
+// The rounds wait on their stream, so a stream under capture cannot take them (ptk.h): refused up front, by name, before
+// anything is enqueued or the capture is disturbed.
+inline int suppress_check_stream(hipStream_t s) {
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &status) != hipSuccess) {
+    (void)hipGetLastError();
+    return PTK_OK;  // (not a stream this call can ask about: the launches below say what is wrong with it)
+  }
+  if (status != hipStreamCaptureStatusNone)
+    return ptkb::fail(PTK_ERR_INVALID,
+                      "suppress_within_self: the stream is being captured -- this call waits on its stream once per round "
+                      "and cannot be captured into a graph");
+  return PTK_OK;
+}
+template <class Round>
+inline int suppress_rounds(uint64_t n_points, uint8_t* d_keep, hipStream_t s, uint32_t* n_rounds, Round&& round) {
+  SuppressCounter counter;
+  int rc = counter.alloc();
+  if (rc == PTK_OK) rc = suppress_init(n_points, d_keep, s);
+  uint32_t rounds = 0, undecided = 1;
+  // (every round decides at least the undecided point of highest key: at most n_points rounds)
+  while (rc == PTK_OK && undecided != 0 && rounds < n_points) {
+    rc = counter.zero(s);
+    if (rc == PTK_OK) rc = round(counter.d_word, rounds > 0);
+    if (rc == PTK_OK) rc = counter.read(s, &undecided);
+    ++rounds;
+  }
+  if (n_rounds != nullptr) *n_rounds = rounds;
+  if (rc == PTK_OK && undecided != 0)
+    return ptkb::fail(PTK_ERR_DEVICE, "suppress_within_self: %u points undecided after %u rounds", undecided, rounds);
+  // (after a failure half-way: nothing of this call is left running on the counter when it goes back to the pool)
+  if (rc != PTK_OK) (void)hipStreamSynchronize(s);
+  return rc;
+}
+void warm_suppress();
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.
 constexpr size_t kSelfStageBytes = size_t(256) << 20;

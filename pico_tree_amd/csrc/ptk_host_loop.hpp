@@ -23,6 +23,7 @@
 #include "pico_tree/internal/align.hpp"
 #include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
+#include "pico_tree/internal/suppress.hpp"
 #include "pico_tree/internal/local_frame.hpp"
 #include "pico_tree/internal/visitors.hpp"
 #include "pico_tree/metric.hpp"
@@ -621,6 +622,34 @@ int ptk_host_align_step(const ptk_tree* t, const float* points, const float* q, 
         [&](int32_t index) { return points + 3 * (size_t)index; }, normals, max_distance,
         [](uint64_t n, auto&& f) { rows_loop(n, f); },
         reinterpret_cast<internal::align_sums*>(out));
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
+// suppress_within_self (ptk.h) as the contract reads: the rows of the self loop above, a sort by key, one greedy pass
+// in descending key (pico_tree/internal/suppress.hpp).
+int ptk_host_suppress_within_self(const ptk_tree* t, const float* points, float radius, const float* radii,
+                                  const float* scores, uint8_t* keep, uint64_t* n_kept) {
+  if (n_kept != nullptr) *n_kept = 0;
+  int rc = ptk_host::check_host_self(t, points, radius, radii);
+  if (rc == PTK_OK) rc = check_scores(scores, t->n_points);
+  if (rc != PTK_OK) return rc;
+  if (keep == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null keep buffer");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    std::vector<std::vector<neighbor_t>> per_row(t->n_points);
+    radius_self_rows(t, flat, view, points, 0, per_row, [&](uint64_t i) { return radii != nullptr ? radii[i] : radius; });
+    const uint64_t kept = internal::suppress_rows(per_row, scores, keep);
+    if (n_kept != nullptr) *n_kept = kept;
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
   } catch (const std::exception& ex) {
