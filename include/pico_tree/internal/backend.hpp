@@ -237,6 +237,10 @@ struct ptk_api<float> {
   static int suppress_within_self(tree const* t, float radius, float const* radii, float const* scores, std::uint8_t* keep) {
     return ptk_suppress_within_self(t, radius, radii, scores, keep, nullptr, nullptr);
   }
+  static int spacing_knn_self(tree const* t, std::uint32_t k, std::uint32_t flags, float ratio, float* mean, float* kth,
+                              std::uint8_t* keep, void* stats) {
+    return ptk_spacing_knn_self(t, k, flags, ratio, mean, kth, keep, static_cast<ptk_spacing_stats*>(stats));
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }
@@ -286,6 +290,10 @@ struct ptk_api<double> {
   }
   static int suppress_within_self(tree const* t, double radius, double const* radii, float const* scores, std::uint8_t* keep) {
     return ptk_search64_suppress_within_self(t, radius, radii, scores, keep, nullptr, nullptr);
+  }
+  static int spacing_knn_self(tree const* t, std::uint32_t k, std::uint32_t flags, float ratio, double* mean, double* kth,
+                              std::uint8_t* keep, void* stats) {
+    return ptk_search64_spacing_knn_self(t, k, flags, ratio, mean, kth, keep, static_cast<ptk_spacing_stats*>(stats));
   }
   static int radius_self(tree const* t, double radius, double const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search64_radius_self(t, radius, radii, sort, offsets, out);

@@ -39,6 +39,7 @@
 #include "internal/flat_tree.hpp"
 #include "internal/local_frame.hpp"
 #include "internal/stream.hpp"
+#include "internal/spacing.hpp"
 #include "internal/suppress.hpp"
 #include "internal/visitors.hpp"
 #include "metric.hpp"
@@ -388,6 +389,33 @@ class kd_tree {
   //! on failure; k == 0 is std::invalid_argument.
   inline void search_knn_self(size_type const k, std::vector<neighbor_type>& out) const {
     batched_knn_self(k, out);
+  }
+
+  //! k-NN spacing of the tree's points (ptk.h, "spacing_knn_self"): mean[i] is
+  //! the mean of the distances of search_knn_self(i, k, ...) -- added in rank
+  //! order from +0 in scalar_type, one division -- and kth[i] (\p kth may be
+  //! null) the last of them; a point without a neighbour gets the largest
+  //! scalar for both.  \p sqrt: the square root of every distance is taken
+  //! first (lengths under metric_l2_squared / metric_se2_squared).  mean, kth:
+  //! size() entries.  Served by the backend (ptk_spacing_knn_self); where it
+  //! refuses (and allow_host_loop is on), and in a build with
+  //! PICO_TREE_HOST_ONLY defined, by a loop over the per-point member and the
+  //! rule of internal/spacing.hpp.  k == 0 is std::invalid_argument.
+  inline void spacing_knn_self(size_type const k, bool const sqrt, scalar_type* mean, scalar_type* kth = nullptr) const {
+    batched_spacing_knn_self(k, sqrt, 0.0f, mean, kth, nullptr, nullptr);
+  }
+
+  //! Statistical outlier removal (PCL's StatisticalOutlierRemoval): keep[i] = 1
+  //! iff point i has a neighbour, a finite mean spacing x_i, and with
+  //! e = x_i - mean: e <= 0 or e * e <= ratio^2 * variance -- mean and sample
+  //! variance of the valid x_i in double over the summation tree of
+  //! internal/align.hpp; \p stats (may be null) receives the record.  keep:
+  //! size() entries.  \p std_ratio must be finite and >= 0
+  //! (std::invalid_argument).  Served as spacing_knn_self.
+  inline void outliers_knn_self(
+      size_type const k, float const std_ratio, bool const sqrt, std::uint8_t* keep, spacing_stats* stats = nullptr) const {
+    std::vector<scalar_type> mean(view().size());
+    batched_spacing_knn_self(k, sqrt, std_ratio, mean.data(), nullptr, keep, stats);
   }
 
   //! Every point's neighbours within \p radius among the other points:
@@ -932,6 +960,45 @@ class kd_tree {
       internal::ptk_check(
           api::knn_self(device(), static_cast<std::uint32_t>(k), reinterpret_cast<typename api::neighbor*>(out.data())),
           "ptk_search_knn_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+  }
+
+  void batched_spacing_knn_self(
+      size_type k, bool sqrt, float ratio, scalar_type* mean, scalar_type* kth, std::uint8_t* keep,
+      spacing_stats* stats) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    if (k == 0) throw std::invalid_argument("pico_tree: spacing_knn_self: k must be >= 1");
+    bool const reduce = keep != nullptr || stats != nullptr;
+    if (reduce && !(ratio >= 0.0f && ratio - ratio == 0.0f)) {
+      throw std::invalid_argument("pico_tree: outliers_knn_self: std_ratio must be finite and >= 0");
+    }
+    size_type const n = view().size();
+    // (the per-point member reduced by the one statement of the rule, then the record and the mask from the means)
+    auto const rows_loop = [&]() {
+      internal::host_rows_loop(n, [&](size_type i) {
+        std::vector<neighbor_type> row;
+        search_knn_self(static_cast<index_type>(i), k, row);
+        scalar_type m, kd;
+        internal::spacing_row<scalar_type>(
+            [&](std::uint32_t j) { return row[j].distance; }, static_cast<std::uint32_t>(row.size()), sqrt, &m, &kd);
+        mean[i] = m;
+        if (kth != nullptr) kth[i] = kd;
+      });
+      if (reduce) internal::spacing_statistics(mean, static_cast<std::uint64_t>(n), ratio, stats, keep);
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(
+          api::spacing_knn_self(
+              device(), static_cast<std::uint32_t>(k), sqrt ? internal::spacing_sqrt : 0u, ratio, mean, kth, keep, stats),
+          "ptk_spacing_knn_self");
     } catch (internal::ptk_unsupported const& refused) {
       if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
       internal::warn_host_loop(refused.what());

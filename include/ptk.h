@@ -540,6 +540,72 @@ int ptk_suppress_within_self(const ptk_tree* tree, float radius, const float* ra
 int ptk_suppress_within_self_device(const ptk_tree* tree, float radius, const float* d_radii, const float* d_scores,
                                     uint8_t* d_keep, uint32_t* n_rounds, void* stream);
 
+/* ---- spacing_knn_self: k-NN spacing and statistical outlier removal of a tree's own points ---------------------------
+ * The mean and the k-th of each point's k nearest-neighbour distances, their global mean and sample variance, and the
+ * keep mask of statistical outlier removal (PCL's StatisticalOutlierRemoval, Open3D's remove_statistical_outlier),
+ * without the rows of ptk_search_knn_self: 4-8 bytes are stored per point instead of 8 k.
+ *   Rows.  Row i is ptk_search_knn_self(tree, k)'s row i: k records, the own entry removed by that call's rule, pad
+ * {-1, FLT_MAX} (DBL_MAX for a float64 tree).  `Real` is the tree's scalar type.  Every operation below is one IEEE
+ * operation of that width, rounded once, in the order written (the units that state it are compiled with
+ * -ffp-contract=off; the one statement is pico_tree/internal/spacing.hpp).
+ *   Per point.
+ *   - m_i = the number of entries of row i whose distance is < FLT_MAX (DBL_MAX).  They are the first m_i entries.
+ *   - d_j = the distance of entry j.  With flag PTK_SPACING_SQRT, d_j = sqrt(distance_j) (correctly rounded).
+ *   - s_i = ((...((+0 + d_0) + d_1) ...) + d_{m_i-1}), in rank order.
+ *   - mean_i = s_i / (Real)m_i.
+ *   - kth_i = d_{m_i-1}.
+ *   - If m_i == 0: mean_i = kth_i = FLT_MAX (DBL_MAX).
+ * The flag turns metric_l2_squared / metric_se2_squared distances into lengths.  The other metrics are called without it.
+ *   Validity.
+ *   - valid_i = m_i > 0 && mean_i - mean_i == 0 (finite).
+ *   - x_i = valid_i ? (double)mean_i : +0.
+ *   Statistics.  Record ptk_spacing_stats is 64 bytes:
+ *       uint64 count, rows;
+ *       double sum, mean, ssd, variance, ratio_squared, reserved;   // reserved = +0
+ *   - rows = n_points; count = #valid.
+ *   - sum is the value of align_step's summation tree over x_0 ... x_{n-1} in original index order.  That tree is defined
+ *     in pico_tree/internal/align.hpp: blocks of 256 entries, align_lane_fold, the butterfly, align_upper_levels.
+ *   - mean = count > 0 ? sum / (double)count : +0.
+ *   - ssd is the same tree over valid_i ? (x_i - mean) * (x_i - mean) : +0.
+ *   - variance = count > 1 ? ssd / (double)(count - 1) : +0.  This is the sample variance, as PCL and Open3D use.
+ *   - ratio_squared = (double)ratio * (double)ratio.
+ * No square root enters the record or the decision.
+ *   Keep.  With e = x_i - mean:
+ *       keep[i] = valid_i && (e <= 0.0 || e * e <= ratio_squared * variance), as uint8 0/1.
+ * This is PCL's "inlier iff mean distance <= mu + ratio * sigma", stated on squares so that host and device need only
+ * + - * /.  `ratio` must be finite and >= 0 whenever keep or stats is asked for; otherwise PTK_ERR_INVALID.
+ *   Arguments.  mean (n_points entries of Real by original index) is required; kth (likewise), keep (n_points uint8) and
+ * stats (one record) may each be NULL.  A flag bit other than PTK_SPACING_SQRT is PTK_ERR_INVALID; the other checks are
+ * ptk_search_knn_self's (k == 0, a null mean with n_points > 0: PTK_ERR_INVALID; a host-only handle: PTK_ERR_DEVICE).
+ * With both keep and stats NULL no reduction runs and no workspace is needed (d_workspace may be NULL, workspace_bytes
+ * 0).  Otherwise the workspace holds a record and the partials of the summation tree's levels (16 bytes per 256 points
+ * and level): ptk_spacing_knn_self_workspace says how many bytes; a null workspace or one smaller than that is
+ * PTK_ERR_INVALID (the message gives both sizes).
+ *   Routes, as ptk_search_knn_self (ptk_debug_self_route): 1 = the direct kernel, whose lanes reduce their register list
+ * as it leaves -- the device form only enqueues on `stream`: no allocation, no wait, and it can be captured --; 2 = the
+ * staged route (dim > 3, the topological metrics, trees deeper than 1 031 levels, k >= 64, every float64 tree): pieces of
+ * the tree's points go through the handle's k-NN search with k + 1 and one lane per row reduces them.  That route
+ * ALLOCATES a block per call and WAITS for `stream` before the reduction is enqueued; it must not be called under a
+ * stream capture.  A refusal of the underlying search is passed on unchanged; ptk_host_spacing_knn_self serves every
+ * float32 handle.  The statistics and the mask run on `stream` in either route, with no host read-back: a level-0 kernel
+ * over mean[] and the upper levels of the tree, a one-lane finish (count, rows, sum, mean), the same for the squared
+ * deviations (ssd, variance, ratio_squared, reserved), an elementwise keep kernel.  Plain vector stores throughout.
+ *   State.  The handle's radius capture and side tables are neither read nor invalidated.  The host forms upload
+ * nothing; they allocate one block per call for the outputs and the workspace and copy the outputs that were asked for
+ * back. */
+#define PTK_SPACING_SQRT 1u
+typedef struct ptk_spacing_stats {
+  uint64_t count;        /* valid points */
+  uint64_t rows;         /* n_points */
+  double sum, mean, ssd, variance, ratio_squared, reserved;
+} ptk_spacing_stats; /* 64 bytes */
+int ptk_spacing_knn_self(const ptk_tree* tree, uint32_t k, uint32_t flags, float ratio, float* mean, float* kth,
+                         uint8_t* keep, ptk_spacing_stats* stats);
+int ptk_spacing_knn_self_device(const ptk_tree* tree, uint32_t k, uint32_t flags, float ratio, float* d_mean, float* d_kth,
+                                uint8_t* d_keep, ptk_spacing_stats* d_stats, void* d_workspace, uint64_t workspace_bytes,
+                                void* stream);
+int ptk_spacing_knn_self_workspace(const ptk_tree* tree, uint64_t* bytes);
+
 /* ---- normals_within_self: PCA normals and curvature of a tree's own points ------------------------------------------
  * The moments of each point's neighbourhood, their covariance, and the local frame of it (surface normal, curvature,
  * eigenvalues), accumulated inside the traversal of the self radius search: no rows are written.  float32 trees with
@@ -793,6 +859,10 @@ int ptk_host_align_step(const ptk_tree* tree, const float* points, const float* 
  * pass in descending key; every metric, the topological ones included) */
 int ptk_host_suppress_within_self(const ptk_tree* tree, const float* points, float radius, const float* radii,
                                   const float* scores, uint8_t* keep, uint64_t* n_kept);
+/* (ptk_spacing_knn_self as the contract reads: the rows of ptk_host_search_knn_self reduced one by one, the record and
+ * the mask from the means; every metric, the topological ones included) */
+int ptk_host_spacing_knn_self(const ptk_tree* tree, const float* points, uint32_t k, uint32_t flags, float ratio,
+                              float* mean, float* kth, uint8_t* keep, ptk_spacing_stats* stats);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 
@@ -916,6 +986,14 @@ int ptk_search64_suppress_within_self(const ptk_tree64* tree, double radius, con
                                       uint8_t* keep, uint64_t* n_kept, uint32_t* n_rounds);
 int ptk_search64_suppress_within_self_device(const ptk_tree64* tree, double radius, const double* d_radii,
                                              const float* d_scores, uint8_t* d_keep, uint32_t* n_rounds, void* stream);
+/* As ptk_spacing_knn_self / _device / _workspace: mean and kth in double, the pad is DBL_MAX.  Every float64 tree takes
+ * the staged route. */
+int ptk_search64_spacing_knn_self(const ptk_tree64* tree, uint32_t k, uint32_t flags, float ratio, double* mean, double* kth,
+                                  uint8_t* keep, ptk_spacing_stats* stats);
+int ptk_search64_spacing_knn_self_device(const ptk_tree64* tree, uint32_t k, uint32_t flags, float ratio, double* d_mean,
+                                         double* d_kth, uint8_t* d_keep, ptk_spacing_stats* d_stats, void* d_workspace,
+                                         uint64_t workspace_bytes, void* stream);
+int ptk_search64_spacing_knn_self_workspace(const ptk_tree64* tree, uint64_t* bytes);
 /* As ptk_search_box. */
 int ptk_search64_box(const ptk_tree64* tree, const double* mins,
                      const double* maxs, uint64_t nb, uint64_t* offsets,

@@ -32,7 +32,7 @@ from . import datasets  # noqa: F401  (re-export)
 
 __all__ = ["KdTree", "KdForest", "save_kd_tree", "load_kd_tree", "Metric", "NEIGHBOR", "NEIGHBOR64", "FRAME", "MOMENTS", "DArray", "DeviceNeighbors", "PtkError",
            "library_path", "device_count", "datasets", "trim_pinned_pool", "registered", "empty_pinned",
-           "ALIGN_SUMS", "AlignSums", "IcpResult", "icp"]
+           "ALIGN_SUMS", "AlignSums", "IcpResult", "icp", "SPACING_STATS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: (PTK_LIBRARY: another build of the same library -- the experiment builds of tools/)
@@ -51,6 +51,11 @@ ALIGN_SUMS = np.dtype([("count", "<u8"), ("rows", "<u8"), ("sum_distance", "<f8"
                        ("sum_p", "<f8", (3,)), ("sum_qp", "<f8", (9,)), ("sum_qq", "<f8"), ("sum_pp", "<f8"),
                        ("jtj", "<f8", (21,)), ("jtr", "<f8", (6,)), ("sum_rr", "<f8")])
 assert ALIGN_SUMS.itemsize == 384
+#: ptk_spacing_stats (ptk.h): the record of KdTree.outliers_knn_self, 64 bytes; PTK_SPACING_SQRT: the flag of the call
+SPACING_STATS = np.dtype([("count", "<u8"), ("rows", "<u8"), ("sum", "<f8"), ("mean", "<f8"), ("ssd", "<f8"),
+                          ("variance", "<f8"), ("ratio_squared", "<f8"), ("reserved", "<f8")])
+assert SPACING_STATS.itemsize == 64
+PTK_SPACING_SQRT = 1
 #: The same record of a tree over float64 points: ``neighbor<int, double>`` is 16 bytes with the
 #: distance at offset 8, which is what the reference binding's PYBIND11_NUMPY_DTYPE yields for it
 #: (_pyco_tree/def_core.hpp:17-18).
@@ -127,6 +132,10 @@ _SIGNATURES = {
                                       c_uint64, c_void_p]),
     "ptk_align_step": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "ptk_host_align_step": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "ptk_spacing_knn_self": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_spacing_knn_self_device": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_uint64, c_void_p]),
+    "ptk_spacing_knn_self_workspace": (c_int, [c_void_p, POINTER(c_uint64)]),
     "ptk_suppress_within_self": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_suppress_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
@@ -168,6 +177,8 @@ _SIGNATURES = {
     "ptk_host_aggregate_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_void_p, c_void_p, c_uint32,
                                           c_uint32, c_void_p, c_void_p]),
     "ptk_host_suppress_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_host_spacing_knn_self": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
     "ptk_host_search_count_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
     "ptk_host_search_radius_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, POINTER(c_void_p)]),
     "ptk_host_search_count_within": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_float, c_uint64, c_void_p]),
@@ -197,6 +208,10 @@ _SIGNATURES = {
     "ptk_search64_knn_self_device": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p]),
     "ptk_search64_cluster_within_self": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
     "ptk_search64_cluster_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_uint64, c_void_p, c_void_p]),
+    "ptk_search64_spacing_knn_self": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_search64_spacing_knn_self_device": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_uint64, c_void_p]),
+    "ptk_search64_spacing_knn_self_workspace": (c_int, [c_void_p, POINTER(c_uint64)]),
     "ptk_search64_suppress_within_self": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_search64_suppress_within_self_device": (c_int, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                                          c_void_p]),
@@ -1619,6 +1634,104 @@ class KdTree:
         self.last_suppress_rounds = int(rounds.value)
         keep = keep.astype(bool)
         return np.flatnonzero(keep).astype(np.int64) if indices else keep
+
+    def _spacing(self, k, sqrt, ratio, want_kth, want_keep, want_stats, device):
+        """One call of ``ptk_spacing_knn_self`` (its float64 / ``_device`` forms): ``(mean, kth, keep, record)``, the
+        outputs that were not asked for None; ``record`` a ``SPACING_STATS`` numpy record."""
+        k = int(k)
+        n = self._npts
+        lib = _load()
+        if sqrt is None:
+            sqrt = self._metric in (Metric.L2Squared, Metric.SE2Squared)
+        flags = PTK_SPACING_SQRT if sqrt else 0
+        ratio = float(ratio)
+        reduce_ = want_keep or want_stats
+        if reduce_ and not 0.0 <= ratio <= float(np.finfo(np.float32).max):  # (the C ABI takes a float)
+            raise ValueError("std_ratio must be finite (as a float32) and >= 0")
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            treal = torch.float64 if self._f64 else torch.float32
+            mean = torch.empty((n,), dtype=treal, device=dev)
+            kth = torch.empty((n,), dtype=treal, device=dev) if want_kth else None
+            keep = torch.empty((n,), dtype=torch.uint8, device=dev) if want_keep else None
+            rec = torch.empty((64,), dtype=torch.uint8, device=dev) if want_stats else None
+            need = ctypes.c_uint64(0)
+            ws = None
+            if reduce_:
+                fn = lib.ptk_search64_spacing_knn_self_workspace if self._f64 else lib.ptk_spacing_knn_self_workspace
+                _check(fn(self._h, byref(need)))
+                ws = torch.empty((max(int(need.value), 1),), dtype=torch.uint8, device=dev)
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            fn = lib.ptk_search64_spacing_knn_self_device if self._f64 else lib.ptk_spacing_knn_self_device
+            _check(fn(self._h, k, flags, ratio, ptr(mean), ptr(kth), ptr(keep), ptr(rec), ptr(ws), int(need.value), stream))
+            if ws is not None:
+                ws.record_stream(torch.cuda.current_stream(dev))
+            record = None
+            if rec is not None:  # (the record is read on the host: the one wait of this form, only where it is asked for)
+                record = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=SPACING_STATS)[0]
+            return mean, kth, keep, record
+        mean = np.empty((n,), dtype=self._real)
+        kth = np.empty((n,), dtype=self._real) if want_kth else None
+        keep = np.empty((n,), dtype=np.uint8) if want_keep else None
+        rec = np.zeros((1,), dtype=SPACING_STATS) if want_stats else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        fn = lib.ptk_search64_spacing_knn_self if self._f64 else lib.ptk_spacing_knn_self
+        self._served(fn(self._h, k, flags, ratio, ptr(mean), ptr(kth), ptr(keep), ptr(rec)),
+                     lambda lib: lib.ptk_host_spacing_knn_self(self._h, self._pts.ctypes.data, k, flags, ratio, ptr(mean),
+                                                               ptr(kth), ptr(keep), ptr(rec)))
+        return mean, kth, keep, rec[0] if rec is not None else None
+
+    def spacing_knn_self(self, k: int, sqrt=None, kth: bool = False, device: bool = False):
+        """``spacing_knn_self(k, sqrt=None, kth=False, device=False)`` -- the mean distance from each tree point to its k
+        nearest OTHER points, and with ``kth=True`` the distance to the k-th of them, without the rows.
+
+        Row i is :meth:`search_knn_self`'s row i; with ``m`` its entries below ``FLT_MAX`` (``DBL_MAX``),
+        ``mean[i] = (((0 + d_0) + d_1) + ...) / m`` and ``kth[i] = d_{m-1}`` in the tree's dtype, one rounding per
+        operation in that order; a point with no neighbour (``npts == 1``) gets ``FLT_MAX`` (``DBL_MAX``) for both.
+        ``sqrt``: take the square root of every distance first (``PTK_SPACING_SQRT``); ``None`` means on iff the metric
+        is ``L2Squared`` or ``SE2Squared``, so that the result is a length.  (``ptk_spacing_knn_self`` /
+        ``ptk_search64_spacing_knn_self``.)
+
+        Returns ``mean`` or ``(mean, kth)``: numpy arrays of the tree's dtype, or with ``device=True`` CUDA tensors on
+        the tree's device, enqueued on the current torch stream.  :meth:`self_route` says whether the call only
+        enqueues (1) or allocates and waits (2).  ``allow_host_loop`` serves float32 trees the device refuses."""
+        mean, kd, _, _ = self._spacing(k, sqrt, 0.0, kth, False, False, device)
+        return (mean, kd) if kth else mean
+
+    def outliers_knn_self(self, k: int, std_ratio: float = 2.0, sqrt=None, indices: bool = False, stats: bool = False,
+                          device: bool = False):
+        """``outliers_knn_self(k, std_ratio=2.0, sqrt=None, indices=False, stats=False, device=False)`` -- statistical
+        outlier removal (PCL's ``StatisticalOutlierRemoval``, Open3D's ``remove_statistical_outlier``): keep the points
+        whose mean distance to their k nearest other points is at most ``mean + std_ratio * stddev`` of those means.
+
+        The means are :meth:`spacing_knn_self`'s.  A point is valid when it has a neighbour and its mean is finite;
+        ``mean`` and ``variance`` (the sample variance) are taken over the valid points in float64 on a fixed summation
+        tree, and ``keep[i] = valid_i and (e <= 0 or e * e <= std_ratio**2 * variance)`` with ``e = mean_i - mean`` --
+        the decision uses no square root and is the same bits on host and device (``ptk.h``).  ``std_ratio`` must be
+        finite and >= 0.
+
+        Returns the ``bool[npts]`` mask, or with ``indices=True`` the kept original indices ascending (``int64``); with
+        ``stats=True`` additionally a dict of the record (``count``, ``rows``, ``sum``, ``mean``, ``ssd``, ``variance``,
+        ``ratio_squared``) plus ``stddev = sqrt(variance)`` and ``threshold = mean + std_ratio * stddev`` (information
+        only), and ``record``, the 64 bytes themselves.  With ``device=True`` the mask is a CUDA tensor, enqueued on the
+        current torch stream; asking for ``stats`` reads 64 bytes back and waits for them."""
+        _, _, keep, rec = self._spacing(k, sqrt, std_ratio, False, True, stats, device)
+        if device:
+            import torch
+            mask = keep.to(torch.bool)
+            out = torch.nonzero(mask).reshape(-1) if indices else mask
+        else:
+            mask = keep.astype(bool)
+            out = np.flatnonzero(mask).astype(np.int64) if indices else mask
+        if not stats:
+            return out
+        info = {name: rec[name].item() for name in SPACING_STATS.names if name != "reserved"}
+        info["stddev"] = float(np.sqrt(info["variance"]))
+        info["threshold"] = info["mean"] + float(np.float32(std_ratio)) * info["stddev"]
+        info["record"] = rec.tobytes()
+        return out, info
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

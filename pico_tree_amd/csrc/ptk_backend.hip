@@ -300,6 +300,7 @@ struct ProcessWarmup {
       ptkf::warm_self();
       ptkf::warm_align();
       ptkf::warm_suppress();
+      ptkf::warm_spacing();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
     });
@@ -2036,6 +2037,64 @@ int ptk_debug_self_route(const ptk_tree* t, uint32_t k, int* route) {
   if (rc != PTK_OK) return rc;
   *route = self_route_of(t, k);
   return PTK_OK;
+}
+
+// ---- spacing_knn_self (ptk.h; the kernels: ptk_kernels_spacing.hpp) ------------------------------------
+
+int ptk_spacing_knn_self_workspace(const ptk_tree* t, uint64_t* bytes) {
+  if (t == nullptr || bytes == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  *bytes = ptkf::spacing_workspace_bytes(t->n_points);
+  return PTK_OK;
+}
+
+// The routes of ptk_search_knn_self_device with the reducing exit (route 1: only enqueues; route 2: allocates and waits),
+// then the statistics on the same stream.  The radius capture and the side tables are neither read nor invalidated.
+int ptk_spacing_knn_self_device(const ptk_tree* t, uint32_t k, uint32_t flags, float ratio, float* d_mean, float* d_kth,
+                                uint8_t* d_keep, ptk_spacing_stats* d_stats, void* d_workspace, uint64_t workspace_bytes,
+                                void* stream) {
+  const bool reduce = d_keep != nullptr || d_stats != nullptr;
+  int rc = check_spacing(t, k, flags, ratio, d_mean, reduce);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  rc = ptkf::spacing_check_workspace(t->n_points, reduce, d_workspace, workspace_bytes);
+  if (rc != PTK_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  if (self_route_of(t, k) == 1) {  // (ranges of leaf positions: no scratch, nothing allocated, nothing waited for)
+    rc = in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+      return ptkf::spacing_self(t, first, n, k, flags, d_mean, d_kth, s);
+    });
+  } else {
+    const float4* recs = t->dim <= 3 ? t->dev.pts : nullptr;
+    const int32_t* index = t->dim <= 3 ? nullptr : t->dev_nd.index;
+    rc = ptkf::self_staged<float, ptk_neighbor>(
+        t->n_points, t->dim, k, s,
+        [&](uint64_t first, uint64_t n, float* d_q) {
+          return ptkf::self_queries(recs, t->dev_nd.pts, t->dim, t->dim, first, n, d_q, s);
+        },
+        [&](const float* d_q, uint64_t n, ptk_neighbor* d_rows) { return ptk_search_knn_device(t, d_q, n, k + 1u, 1.0f, d_rows, s); },
+        [&](const ptk_neighbor* d_rows, uint64_t first, uint64_t n) {
+          return ptkf::spacing_rows(reinterpret_cast<const ptk::Neighbor*>(d_rows), recs, index, first, n, k, flags, d_mean,
+                                    d_kth, s);
+        });
+  }
+  if (rc != PTK_OK || !reduce) return rc;
+  return ptkf::spacing_statistics(d_mean, t->n_points, ratio, d_keep, d_stats, static_cast<char*>(d_workspace), s);
+}
+
+// The host form: nothing goes up; the outputs that were asked for come down from a block of the call's own.
+int ptk_spacing_knn_self(const ptk_tree* t, uint32_t k, uint32_t flags, float ratio, float* mean, float* kth, uint8_t* keep,
+                         ptk_spacing_stats* stats) {
+  const int rc = check_spacing(t, k, flags, ratio, mean, keep != nullptr || stats != nullptr);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  return ptkf::spacing_host_form<float>(t->n_points, mean, kth, keep, stats,
+                                        [&](float* d_mean, float* d_kth, uint8_t* d_keep, ptk_spacing_stats* d_stats,
+                                            void* d_ws, uint64_t ws_bytes) {
+                                          return ptk_spacing_knn_self_device(t, k, flags, ratio, d_mean, d_kth, d_keep, d_stats,
+                                                                             d_ws, ws_bytes, nullptr);
+                                        });
 }
 
 // ---- neighbour counts within a radius ---------------------------------------

@@ -675,6 +675,19 @@ inline int check_knn_self(const Tree* t, uint32_t k, const void* out) {
   if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
   return PTK_OK;
 }
+// spacing_knn_self (ptk.h): check_knn_self with the means as the output, then the flags and -- where the mask or the
+// record is asked for -- the ratio.  (The host loop, which takes host-only handles, spells the same refusals.)
+inline int check_spacing_values(uint32_t flags, float ratio, bool reduce) {
+  if ((flags & ~(uint32_t)PTK_SPACING_SQRT) != 0u) return fail(PTK_ERR_INVALID, "spacing_knn_self: unknown flag bits 0x%x", flags);
+  if (reduce && !(ratio >= 0.0f && ratio - ratio == 0.0f))
+    return fail(PTK_ERR_INVALID, "spacing_knn_self: ratio must be finite and >= 0");
+  return PTK_OK;
+}
+template <class Tree>
+inline int check_spacing(const Tree* t, uint32_t k, uint32_t flags, float ratio, const void* mean, bool reduce) {
+  const int rc = check_knn_self(t, k, mean);
+  return rc != PTK_OK ? rc : check_spacing_values(flags, ratio, reduce);
+}
 template <class Tree>
 inline int check_count_within(const Tree* t, const void* q, uint64_t nq, double radius, const void* counts) {
   int rc = check_search(t, q, nq);

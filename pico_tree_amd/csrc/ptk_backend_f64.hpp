@@ -965,6 +965,52 @@ int ptk_search64_knn_self(const ptk_tree64* t, uint32_t k, ptk_neighbor64* out) 
   });
 }
 
+// spacing_knn_self (ptk.h): the staged route of the search above with the reducing `drop` step, then the
+// statistics on the same stream.
+int ptk_search64_spacing_knn_self_workspace(const ptk_tree64* t, uint64_t* bytes) {
+  if (t == nullptr || bytes == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  *bytes = ptkf::spacing_workspace_bytes(t->n_points);
+  return PTK_OK;
+}
+
+int ptk_search64_spacing_knn_self_device(const ptk_tree64* t, uint32_t k, uint32_t flags, float ratio, double* d_mean,
+                                         double* d_kth, uint8_t* d_keep, ptk_spacing_stats* d_stats, void* d_workspace,
+                                         uint64_t workspace_bytes, void* stream) {
+  const bool reduce = d_keep != nullptr || d_stats != nullptr;
+  int rc = check_spacing(t, k, flags, ratio, d_mean, reduce);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  rc = ptkf::spacing_check_workspace(t->n_points, reduce, d_workspace, workspace_bytes);
+  if (rc != PTK_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = ptkf::self_staged<double, ptk_neighbor64>(
+      t->n_points, t->dim, k, s,
+      [&](uint64_t first, uint64_t n, double* d_q) {
+        return ptkf::self_queries64(t->dev.pts, t->dev.stride, t->dim, first, n, d_q, s);
+      },
+      [&](const double* d_q, uint64_t n, ptk_neighbor64* d_rows) { return ptk_search64_knn_device(t, d_q, n, k + 1u, 1.0, d_rows, s); },
+      [&](const ptk_neighbor64* d_rows, uint64_t first, uint64_t n) {
+        return ptkf::spacing_rows64(d_rows, t->dev.index, first, n, k, flags, d_mean, d_kth, s);
+      });
+  if (rc != PTK_OK || !reduce) return rc;
+  return ptkf::spacing_statistics64(d_mean, t->n_points, ratio, d_keep, d_stats, static_cast<char*>(d_workspace), s);
+}
+
+int ptk_search64_spacing_knn_self(const ptk_tree64* t, uint32_t k, uint32_t flags, float ratio, double* mean, double* kth,
+                                  uint8_t* keep, ptk_spacing_stats* stats) {
+  const int rc = check_spacing(t, k, flags, ratio, mean, keep != nullptr || stats != nullptr);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  return ptkf::spacing_host_form<double>(t->n_points, mean, kth, keep, stats,
+                                         [&](double* d_mean, double* d_kth, uint8_t* d_keep, ptk_spacing_stats* d_stats,
+                                             void* d_ws, uint64_t ws_bytes) {
+                                           return ptk_search64_spacing_knn_self_device(t, k, flags, ratio, d_mean, d_kth, d_keep,
+                                                                                       d_stats, d_ws, ws_bytes, nullptr);
+                                         });
+}
+
 // search_knn_within (ptk.h).  The list starts at radius * (1 + 2^-10) (as the float32 search); DBL_MAX
 // -- the plain search, masked at store -- for metric_lpinf / metric_lninf, trees deeper than the margin covers
 // (~2 000 levels), a radius that is subnormal or whose margin overflows.

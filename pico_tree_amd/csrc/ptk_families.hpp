@@ -262,6 +262,71 @@ inline int suppress_rounds(uint64_t n_points, uint8_t* d_keep, hipStream_t s, ui
   return rc;
 }
 void warm_suppress();
+// ptk_family_spacing.hip: spacing_knn_self (ptk_kernels_spacing.hpp).  spacing_self: route 1, the
+// traversal of knn_self on leaf positions [first, first + n) with the reducing exit -- d_mean[index], d_kth[index] (may be
+// null).  spacing_rows*: the `drop` step of the staged route over rows of k + 1 records.  spacing_statistics*: the record
+// and / or the mask (either may be null, not both) from the n means, enqueued on `s`; d_workspace holds
+// spacing_workspace_bytes(n): a record (the mask needs one where the caller keeps none) and per level of the summation
+// tree its partials and counts.
+int spacing_self(const ptk_tree* t, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, float* d_mean, float* d_kth,
+                 hipStream_t s);
+int spacing_rows(const ptk::Neighbor* rows, const float4* recs, const int32_t* index, uint64_t first, uint64_t n, uint32_t k,
+                 uint32_t flags, float* d_mean, float* d_kth, hipStream_t s);
+int spacing_rows64(const void* rows, const int32_t* index, uint64_t first, uint64_t n, uint32_t k, uint32_t flags,
+                   double* d_mean, double* d_kth, hipStream_t s);
+constexpr size_t kSpacingRecordBytes = 256;  // (the record's slot at the head of the workspace)
+constexpr size_t kSpacingEntryBytes = 16;    // (a partial and a count)
+size_t spacing_workspace_bytes(uint64_t n);
+int spacing_statistics(const float* d_mean, uint64_t n, float ratio, uint8_t* d_keep, ptk_spacing_stats* d_stats,
+                       char* d_workspace, hipStream_t s);
+int spacing_statistics64(const double* d_mean, uint64_t n, float ratio, uint8_t* d_keep, ptk_spacing_stats* d_stats,
+                         char* d_workspace, hipStream_t s);
+void warm_spacing();
+// The workspace check of the _device forms of either precision: none is needed where neither the mask nor the record is
+// asked for.
+inline int spacing_check_workspace(uint64_t n, bool reduce, const void* d_workspace, uint64_t workspace_bytes) {
+  if (!reduce || n == 0) return PTK_OK;
+  const size_t need = spacing_workspace_bytes(n);
+  if (d_workspace == nullptr) return ptkb::fail(PTK_ERR_INVALID, "spacing_knn_self: null workspace");
+  if (workspace_bytes < need)
+    return ptkb::fail(PTK_ERR_INVALID,
+                      "spacing_knn_self: the workspace holds %llu bytes, %llu points need %llu (ptk_spacing_knn_self_workspace)",
+                      (unsigned long long)workspace_bytes, (unsigned long long)n, (unsigned long long)need);
+  return PTK_OK;
+}
+// The host-buffer form of either precision: one block per call holds the outputs that were asked for and the workspace;
+// `device(d_mean, d_kth, d_keep, d_stats, d_workspace, workspace_bytes)` is the _device form on the null stream; the
+// outputs come down with blocking copies.  Nothing goes up.  The caller has set the device.
+template <class Real, class Device>
+inline int spacing_host_form(uint64_t n, Real* mean, Real* kth, uint8_t* keep, ptk_spacing_stats* stats, Device&& device) {
+  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const bool reduce = keep != nullptr || stats != nullptr;
+  const size_t real_bytes = (size_t)n * sizeof(Real);
+  const size_t o_kth = pad(real_bytes);
+  const size_t o_keep = o_kth + (kth != nullptr ? pad(real_bytes) : 0);
+  const size_t o_stats = o_keep + (keep != nullptr ? pad((size_t)n) : 0);
+  const size_t o_ws = o_stats + (stats != nullptr ? pad(sizeof(ptk_spacing_stats)) : 0);
+  const size_t ws_bytes = reduce ? spacing_workspace_bytes(n) : 0;
+  ptkb::DeviceBlock block;
+  if (block.alloc(o_ws + ws_bytes + 256) != hipSuccess) {
+    (void)hipGetLastError();
+    return ptkb::fail(PTK_ERR_NOMEM, "out of device memory (the outputs of spacing_knn_self)");
+  }
+  char* base = block.as<char>();
+  int rc = device(reinterpret_cast<Real*>(base), kth != nullptr ? reinterpret_cast<Real*>(base + o_kth) : nullptr,
+                  keep != nullptr ? reinterpret_cast<uint8_t*>(base + o_keep) : nullptr,
+                  stats != nullptr ? reinterpret_cast<ptk_spacing_stats*>(base + o_stats) : nullptr,
+                  reduce ? static_cast<void*>(base + o_ws) : nullptr, (uint64_t)ws_bytes);
+  // (the block is freed when this returns: everything enqueued on it has to be done -- also after a refusal half-way)
+  hipError_t he = hipStreamSynchronize(nullptr);
+  if (rc != PTK_OK) return rc;
+  if (he == hipSuccess) he = hipMemcpy(mean, base, real_bytes, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && kth != nullptr) he = hipMemcpy(kth, base + o_kth, real_bytes, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && keep != nullptr) he = hipMemcpy(keep, base + o_keep, (size_t)n, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && stats != nullptr) he = hipMemcpy(stats, base + o_stats, sizeof(ptk_spacing_stats), hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return ptkb::fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  return PTK_OK;
+}
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.
 constexpr size_t kSelfStageBytes = size_t(256) << 20;

@@ -24,6 +24,7 @@
 #include "pico_tree/internal/cluster.hpp"
 #include "pico_tree/internal/flat_search.hpp"
 #include "pico_tree/internal/suppress.hpp"
+#include "pico_tree/internal/spacing.hpp"
 #include "pico_tree/internal/local_frame.hpp"
 #include "pico_tree/internal/visitors.hpp"
 #include "pico_tree/metric.hpp"
@@ -303,19 +304,18 @@ int ptk_host_search_knn(const ptk_tree* t, const float* points, const float* q, 
 
 // search_knn_self (ptk.h) as it is written: the reference's search_knn row of m = min(k + 1, n_points) entries for each
 // tree point, the entry the rule names removed (the first whose index is the row's, else the last), the row padded
-// with {-1, FLT_MAX}.
-int ptk_host_search_knn_self(const ptk_tree* t, const float* points, uint32_t k, ptk_neighbor* out) {
-  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
-  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
-  if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+// with {-1, FLT_MAX} to `width` records (k, or fewer where the caller reads no more: a row holds at most n_points - 1
+// entries).  `dest(i)`: where row i is written; `done(i, row)` is called once it stands there.
+extern "C++" {
+namespace ptk_host {
+template <class Dest, class Done>
+int knn_self_rows(const ptk_tree* t, const float* points, uint32_t k, uint32_t width, Dest&& dest, Done&& done) {
   try {
-    using namespace ptk_host;
     const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
     const flat_t& flat = *flat_holder;
     if (topological_without_bounds(t, flat)) return fail(PTK_ERR_INVALID, "this tree has no outer bounds (ptk_tree_set_outer_bounds)");
     space_t space(points, t->n_points, t->dim);
     view_t view(space);
-    auto* rows = reinterpret_cast<neighbor_t*>(out);
     const uint32_t m = (uint32_t)std::min<uint64_t>((uint64_t)k + 1, t->n_points);
     const float fmax = std::numeric_limits<float>::max();
     rows_loop(t->n_points, [&](uint64_t i) {
@@ -329,17 +329,64 @@ int ptk_host_search_knn_self(const ptk_tree* t, const float* points, uint32_t k,
           drop = j;
           break;
         }
-      neighbor_t* b = rows + i * k;
+      neighbor_t* b = dest(i);
       uint32_t n = 0;
       for (uint32_t j = 0; j < found; ++j)
         if (j != drop && full[j].distance < fmax) b[n++] = full[j];
-      for (; n < k; ++n) b[n] = neighbor_t{-1, fmax};
+      for (; n < width; ++n) b[n] = neighbor_t{-1, fmax};
+      done(i, b);
     });
   } catch (const std::bad_alloc&) {
     return fail(PTK_ERR_NOMEM, "out of host memory");
   } catch (const std::exception& ex) {
     return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
   }
+  return PTK_OK;
+}
+}  // namespace ptk_host
+}  // extern "C++"
+
+int ptk_host_search_knn_self(const ptk_tree* t, const float* points, uint32_t k, ptk_neighbor* out) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (out == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+  auto* rows = reinterpret_cast<ptk_host::neighbor_t*>(out);
+  return ptk_host::knn_self_rows(t, points, k, k, [&](uint64_t i) { return rows + i * k; },
+                                 [](uint64_t, const ptk_host::neighbor_t*) {});
+}
+
+// spacing_knn_self (ptk.h) as the contract reads: each row of the loop above reduced by the rule of
+// pico_tree/internal/spacing.hpp, then the record and the mask from the means.
+int ptk_host_spacing_knn_self(const ptk_tree* t, const float* points, uint32_t k, uint32_t flags, float ratio, float* mean,
+                              float* kth, uint8_t* keep, ptk_spacing_stats* stats) {
+  if (t == nullptr || points == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  if (k == 0) return fail(PTK_ERR_INVALID, "k must be >= 1");
+  if (k == 0xFFFFFFFFu) return fail(PTK_ERR_INVALID, "k + 1 does not fit 32 bits");
+  if (mean == nullptr && t->n_points > 0) return fail(PTK_ERR_INVALID, "null output buffer");
+  int rc = check_spacing_values(flags, ratio, keep != nullptr || stats != nullptr);
+  if (rc != PTK_OK) return rc;
+  using namespace ptk_host;
+  const bool root = (flags & PTK_SPACING_SQRT) != 0u;
+  // (a row holds at most n_points - 1 entries, whatever k is: the buffer and the fold are as wide as that, and the buffer
+  // lives as long as the row)
+  const uint32_t width = (uint32_t)std::min<uint64_t>(k, t->n_points);
+  rc = ptk_host::knn_self_rows(
+      t, points, k, width,
+      [&](uint64_t) {
+        thread_local std::vector<ptk_host::neighbor_t> row;
+        row.resize(width);
+        return row.data();
+      },
+      [&](uint64_t i, const ptk_host::neighbor_t* row) {
+        float m, kd;
+        internal::spacing_row<float>([&](uint32_t j) { return row[j].distance; }, width, root, &m, &kd);
+        mean[i] = m;
+        if (kth != nullptr) kth[i] = kd;
+      });
+  if (rc != PTK_OK) return rc;
+  static_assert(sizeof(ptk_spacing_stats) == sizeof(internal::spacing_stats), "record layout");
+  if (keep != nullptr || stats != nullptr)
+    internal::spacing_statistics(mean, t->n_points, ratio, reinterpret_cast<internal::spacing_stats*>(stats), keep);
   return PTK_OK;
 }
 
