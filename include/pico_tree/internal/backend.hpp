@@ -241,6 +241,11 @@ struct ptk_api<float> {
                               std::uint8_t* keep, void* stats) {
     return ptk_spacing_knn_self(t, k, flags, ratio, mean, kth, keep, static_cast<ptk_spacing_stats*>(stats));
   }
+  // (edges: n_points - 1 records of 12 bytes, {uint32 lo, uint32 hi, float w}; float32 trees only: ptk.h)
+  static int mst_within_self(tree const* t, float radius, float const* core, void* edges, std::uint64_t* n_edges,
+                             std::int32_t* labels) {
+    return ptk_mst_within_self(t, radius, core, static_cast<ptk_mst_edge*>(edges), n_edges, labels, nullptr);
+  }
   static int radius_self(tree const* t, float radius, float const* radii, int sort, std::uint64_t* offsets, neighbor** out) {
     return ptk_search_radius_self(t, radius, radii, sort, offsets, out);
   }

@@ -38,6 +38,7 @@
 #include "internal/flat_search.hpp"
 #include "internal/flat_tree.hpp"
 #include "internal/local_frame.hpp"
+#include "internal/mst.hpp"
 #include "internal/stream.hpp"
 #include "internal/spacing.hpp"
 #include "internal/suppress.hpp"
@@ -468,6 +469,26 @@ class kd_tree {
       std::vector<scalar_type> const& radii, std::int32_t* labels, size_type const min_neighbors = 0) const {
     check_radii(radii, view().size());
     batched_cluster_within_self(scalar_type(0), radii.data(), labels, min_neighbors);
+  }
+
+  //! The minimum spanning forest of the fixed-radius graph over the tree's
+  //! points (float points, metric_l2_squared or metric_l1).  {i, j} is an edge
+  //! iff j is in search_radius_self's row i or i in row j; its weight is the
+  //! row's distance, or with \p core (size() float entries by original index,
+  //! in the metric's unit, none NaN or negative: std::invalid_argument)
+  //! max(d, core[i], core[j]), and the edge then exists only if that is below
+  //! \p radius too.  Edges are ordered by (bits(w), lo, hi)
+  //! (internal/mst.hpp), which makes the forest unique.  edges: size() - 1
+  //! records; returned ascending in that order, the return value is their
+  //! number (size() minus the number of components).  labels (may be null):
+  //! size() entries, the smallest index of the point's component.  Served by
+  //! the backend (ptk_mst_within_self); where it refuses (and allow_host_loop
+  //! is on), and in a build with PICO_TREE_HOST_ONLY defined, by the per-point
+  //! member plus Kruskal.
+  inline size_type mst_within_self(
+      scalar_type const radius, internal::mst_edge* edges, float const* core = nullptr,
+      std::int32_t* labels = nullptr) const {
+    return batched_mst_within_self(radius, core, edges, labels);
   }
 
   //! Greedy radius suppression of the tree's points: thinning to an r-separated
@@ -1092,6 +1113,35 @@ class kd_tree {
       rows_loop();
     }
 #endif
+  }
+
+  size_type batched_mst_within_self(
+      scalar_type radius, float const* core, internal::mst_edge* edges, std::int32_t* labels) const {
+    static_assert(accelerated, "BATCHED_SEARCH_NEEDS_A_BACKEND_METRIC_FLOAT_OR_DOUBLE_INT");
+    static_assert(std::is_same<scalar_type, float>::value, "MST_WITHIN_SELF_NEEDS_FLOAT_POINTS");
+    size_type const n = view().size();
+    if (core != nullptr && internal::mst_first_bad_core(core, n) != n) {
+      throw std::invalid_argument("pico_tree: core must not hold a NaN or a negative value");
+    }
+    if (!(radius >= scalar_type(0))) throw std::invalid_argument("pico_tree: radius must be >= 0 (and not NaN)");
+    std::uint64_t count = 0;
+    auto const rows_loop = [&]() {
+      std::vector<std::vector<neighbor_type>> rows(n);
+      internal::host_rows_loop(n, [&](size_type i) { search_radius_self(static_cast<index_type>(i), radius, rows[i]); });
+      count = internal::mst_rows(rows, radius, core, edges, labels);
+    };
+#ifdef PICO_TREE_HOST_ONLY
+    rows_loop();
+#else
+    try {
+      internal::ptk_check(api::mst_within_self(device(), radius, core, edges, &count, labels), "ptk_mst_within_self");
+    } catch (internal::ptk_unsupported const& refused) {
+      if (!internal::host_loop_flag().load()) throw;  // (as batched_knn)
+      internal::warn_host_loop(refused.what());
+      rows_loop();
+    }
+#endif
+    return static_cast<size_type>(count);
   }
 
   void batched_suppress_within_self(

@@ -606,6 +606,59 @@ int ptk_spacing_knn_self_device(const ptk_tree* tree, uint32_t k, uint32_t flags
                                 void* stream);
 int ptk_spacing_knn_self_workspace(const ptk_tree* tree, uint64_t* bytes);
 
+/* ---- mst_within_self: the minimum spanning forest of a tree's own points ----------------------------------------------
+ * The minimum spanning forest (MSF) of the fixed-radius graph over the tree's points: cutting its edges at any r' <= r
+ * gives exactly the components ptk_cluster_within_self(r', 0) gives -- the single-linkage dendrogram, for all radii at
+ * once -- and with the core distances of ptk_spacing_knn_self (kth) it is HDBSCAN's tree under the mutual-reachability
+ * weight.  No rows are written: Boruvka rounds of a k = 1 search that ignores the point's own component, on the device.
+ *   Inputs.  A float32 handle; a scalar `radius` (there are no per-point radii); `core`: NULL, or n_points float32
+ * entries by ORIGINAL point index in the metric's unit (squared under metric_l2_squared: ptk_spacing_knn_self's kth
+ * WITHOUT PTK_SPACING_SQRT).
+ *   Graph.  Let row i be row i of ptk_search_radius_self(tree, radius): exact, strict <, the handle's metric and unit, the
+ * own entry removed.  {i, j} is an edge iff j is in row i or i is in row j (as ptk_cluster_within_self).  Its weight is
+ * w = d, the row's distance bits, when core is NULL; otherwise w = max(d, core[i], core[j]) as float32, and the edge
+ * exists only if additionally w < radius.
+ *   Order.  Edges are ordered by the triple (bits(w), lo, hi), lo = min(i, j), hi = max(i, j).  Weights are non-negative,
+ * so the bit order is the value order; the triples are distinct, so the MSF is unique.  Equal distances are decided by
+ * this rule only, never by traversal order.
+ *   Result.  n_edges = n_points minus the number of components.  An edge record is 12 bytes, ptk_mst_edge
+ * {uint32 lo, uint32 hi, float w}; the edge buffer holds n_points - 1 records (n_points <= 1: no edges, the buffer may be
+ * NULL).  labels (may be NULL; int32 by original index): the smallest original index of the point's component.  The
+ * host-buffer form and the host loop return the edges ASCENDING in that order, so two calls give identical bytes.  THE
+ * _device FORM WRITES THE SAME SET IN UNSPECIFIED ORDER (it may differ between two calls) and leaves the count in the
+ * first 4 bytes of the workspace (uint32); sort by (bits(w), lo, hi) for the host forms' bytes.
+ *   Values.  radius = 0 gives no edges and labels[i] = i.  +inf and FLT_MAX are valid and give the Euclidean MST of a
+ * connected cloud; a pair whose distance overflows to inf is no edge (the test is strict <).  A NaN or negative radius
+ * is PTK_ERR_INVALID.  A NaN or negative core entry is PTK_ERR_INVALID in the host-buffer form and the host loop (the
+ * message names the row); the _device form cannot look: there such a point has no edges.
+ *   Where the rows are not symmetric (a tree read from a stream that does not belong to its points) the call still ends,
+ * writes a spanning forest of the same components (labels equal ptk_cluster_within_self(radius, 0)'s) and every edge
+ * written is an edge of the graph.  MINIMALITY is promised only where the rows are symmetric.
+ *   Where the device serves it: float32 handles with dim <= 3 under metric_l2_squared and metric_l1 (the metrics whose box
+ * distance is a lower bound of the point distance), not of the deep stack class.  Everything else is
+ * PTK_ERR_UNSUPPORTED, naming the reason and ptk_host_mst_within_self, which serves every float32 handle under those two
+ * metrics.  A host-only handle is PTK_ERR_DEVICE.
+ *   Rounds.  Every point starts as a component.  A round finds every component's minimum edge to another component (a
+ * per-branch table of "all of one component" lets the search skip whole subtrees of its own component), links the
+ * components in a lock-free union-find, and relabels.  On symmetric rows there are at most ceil(log2 n) + 1 rounds.
+ * n_rounds (may be NULL) is information only.
+ *   State and waiting, as ptk_suppress_within_self.  The _device form WAITS on `stream` once per round and reads 4 bytes
+ * back, with the counter from the library's per-device pool; a `stream` that is being captured is PTK_ERR_INVALID, by
+ * name, before anything is enqueued.  The radius capture is neither read nor invalidated; the count side table is built
+ * on first use.  Nothing else is allocated: the caller passes d_workspace of at least ptk_mst_within_self_workspace
+ * bytes (a shorter one is PTK_ERR_INVALID).  The host form allocates one block per call; core goes up, the edges and
+ * labels come down. */
+typedef struct ptk_mst_edge {
+  uint32_t lo, hi;
+  float w;
+} ptk_mst_edge; /* 12 bytes */
+int ptk_mst_within_self(const ptk_tree* tree, float radius, const float* core, ptk_mst_edge* edges, uint64_t* n_edges,
+                        int32_t* labels, uint32_t* n_rounds);
+int ptk_mst_within_self_device(const ptk_tree* tree, float radius, const float* d_core, ptk_mst_edge* d_edges,
+                               int32_t* d_labels, void* d_workspace, uint64_t workspace_bytes, uint64_t* n_edges,
+                               uint32_t* n_rounds, void* stream);
+int ptk_mst_within_self_workspace(const ptk_tree* tree, uint64_t* bytes);
+
 /* ---- normals_within_self: PCA normals and curvature of a tree's own points ------------------------------------------
  * The moments of each point's neighbourhood, their covariance, and the local frame of it (surface normal, curvature,
  * eigenvalues), accumulated inside the traversal of the self radius search: no rows are written.  float32 trees with
@@ -863,6 +916,12 @@ int ptk_host_suppress_within_self(const ptk_tree* tree, const float* points, flo
  * the mask from the means; every metric, the topological ones included) */
 int ptk_host_spacing_knn_self(const ptk_tree* tree, const float* points, uint32_t k, uint32_t flags, float ratio,
                               float* mean, float* kth, uint8_t* keep, ptk_spacing_stats* stats);
+/* (ptk_mst_within_self as the contract reads: the rows of ptk_host_search_radius_self, the edges sorted by
+ * (bits(w), lo, hi), Kruskal with a union-find; every float32 handle under metric_l2_squared and metric_l1, any dim, the
+ * deep stack class included; another metric is PTK_ERR_UNSUPPORTED.  It keeps every row at once: memory grows with the
+ * rows) */
+int ptk_host_mst_within_self(const ptk_tree* tree, const float* points, float radius, const float* core,
+                             ptk_mst_edge* edges, uint64_t* n_edges, int32_t* labels);
 int ptk_host_search_box(const ptk_tree* tree, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out);                            /* *out: ptk_free */
 

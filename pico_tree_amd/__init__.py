@@ -32,7 +32,7 @@ from . import datasets  # noqa: F401  (re-export)
 
 __all__ = ["KdTree", "KdForest", "save_kd_tree", "load_kd_tree", "Metric", "NEIGHBOR", "NEIGHBOR64", "FRAME", "MOMENTS", "DArray", "DeviceNeighbors", "PtkError",
            "library_path", "device_count", "datasets", "trim_pinned_pool", "registered", "empty_pinned",
-           "ALIGN_SUMS", "AlignSums", "IcpResult", "icp", "SPACING_STATS"]
+           "ALIGN_SUMS", "AlignSums", "IcpResult", "icp", "SPACING_STATS", "MST_EDGE"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 #: (PTK_LIBRARY: another build of the same library -- the experiment builds of tools/)
@@ -61,6 +61,9 @@ PTK_SPACING_SQRT = 1
 #: (_pyco_tree/def_core.hpp:17-18).
 NEIGHBOR64 = np.dtype({"names": ["index", "distance"], "formats": ["<i4", "<f8"], "offsets": [0, 8],
                        "itemsize": 16})
+
+#: One edge of :meth:`KdTree.mst_within_self` (``ptk_mst_edge``): 12 bytes.
+MST_EDGE = np.dtype([("lo", "<u4"), ("hi", "<u4"), ("w", "<f4")])
 
 PTK_OK = 0
 PTK_DEVICE_CURRENT = -1
@@ -136,6 +139,11 @@ _SIGNATURES = {
     "ptk_spacing_knn_self_device": (c_int, [c_void_p, c_uint32, c_uint32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_uint64, c_void_p]),
     "ptk_spacing_knn_self_workspace": (c_int, [c_void_p, POINTER(c_uint64)]),
+    "ptk_mst_within_self": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_mst_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p,
+                                           c_void_p, c_void_p]),
+    "ptk_mst_within_self_workspace": (c_int, [c_void_p, POINTER(c_uint64)]),
+    "ptk_host_mst_within_self": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_suppress_within_self": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_suppress_within_self_device": (c_int, [c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ptk_search_count_within_self": (c_int, [c_void_p, c_float, c_void_p, c_uint64, c_void_p]),
@@ -1732,6 +1740,101 @@ class KdTree:
         info["threshold"] = info["mean"] + float(np.float32(std_ratio)) * info["stddev"]
         info["record"] = rec.tobytes()
         return out, info
+
+    def _mst_core(self, core, device):
+        """The core distances of :meth:`mst_within_self`: None, a contiguous float32 host array of ``npts`` entries, none
+        NaN or negative, or -- ``device``: the torch device of a device call -- a contiguous float32 CUDA tensor on it,
+        taken as it is (a host array-like is checked and uploaded)."""
+        if core is None:
+            return None
+        n = self._npts
+        if device is not None and _is_torch(core) and core.is_cuda:
+            import torch
+            if core.device != device:
+                raise ValueError(f"core must be on the tree's device ({device}), not on {core.device}")
+            if core.dtype != torch.float32 or core.dim() != 1 or core.shape[0] != n or not core.is_contiguous():
+                raise ValueError(f"core must be a contiguous 1-D float32 tensor of {n} entries, one per tree point")
+            return core
+        if _is_torch(core):
+            if core.is_cuda:
+                raise ValueError("core: a host call takes a host array, not a CUDA tensor")
+            core = core.numpy()
+        try:
+            host = np.ascontiguousarray(core, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"core must be None or an array of {n} numbers") from None
+        if host.ndim != 1 or host.shape[0] != n:
+            raise ValueError(f"core must be a 1-D array of {n} entries, one per tree point, not {tuple(host.shape)}")
+        bad = np.flatnonzero(~(host >= 0))
+        if len(bad):
+            raise ValueError(f"core[{int(bad[0])}] must be >= 0 (and not NaN)")
+        if device is not None:
+            import torch
+            return torch.from_numpy(host if host.flags.writeable else host.copy()).to(device)
+        return host
+
+    def mst_within_self(self, radius=np.inf, core=None, labels: bool = False, device: bool = False):
+        """``mst_within_self(radius=inf, core=None, labels=False, device=False)`` -- the minimum spanning forest of the
+        fixed-radius graph over the tree's points: the single-linkage dendrogram for every radius up to ``radius`` at once,
+        and with ``core`` HDBSCAN's mutual-reachability tree.
+
+        With row i being :meth:`search_radius_self`'s row i at ``radius`` (strict, the metric's own unit -- squared under
+        ``L2Squared``), ``{i, j}`` is an edge iff j is in row i or i in row j.  Its weight is the row's distance, or with
+        ``core`` (``npts`` float32 values by original index, in the same unit: :meth:`spacing_knn_self`'s ``kth`` with
+        ``sqrt=False``) ``max(d, core[i], core[j])``, and the edge then exists only if that is below ``radius`` too.  Edges
+        are ordered by ``(bits(w), lo, hi)`` with ``lo < hi`` the two indices: the triples are distinct, so the forest is
+        unique, and ties are decided by this rule alone.  Cutting the forest at any ``r' <= radius`` (keep ``w < r'``)
+        gives the components of ``cluster_within_self(r', 0)``.  ``radius=inf`` gives the Euclidean minimum spanning
+        tree of the cloud.  (``ptk_mst_within_self``.)
+
+        Returns a structured array (:data:`MST_EDGE`: ``lo``, ``hi`` uint32, ``w`` float32) of ``npts`` minus the number
+        of components records, ascending in that order; with ``labels=True`` also ``int32[npts]``, the smallest index
+        of each point's component.  With ``device=True`` the edges are three CUDA tensors ``(lo, hi, w)`` (int32, int32,
+        float32) in the same order, ``core`` may be a float32 CUDA tensor (a NaN or negative entry then gives a point
+        without edges), and the rounds run on the current torch stream; like :meth:`suppress_within_self` the call
+        waits on that stream once per round and cannot be captured into a graph.  ``tree.last_mst_rounds`` holds the
+        rounds launched (information only).  Served for float32 trees with ``sdim <= 3`` under ``L2Squared`` and ``L1``;
+        the rest is refused (``allow_host_loop`` serves float32 trees under those two metrics)."""
+        n = self._npts
+        lib = _load()
+        if self._f64:
+            raise PtkError(PTK_ERR_UNSUPPORTED, "mst_within_self: float64 trees are not served (the host loop, "
+                           "ptk_host_mst_within_self, serves float32 trees)")
+        r = np.float32(radius)
+        rounds = ctypes.c_uint32(0)
+        count = c_uint64(0)
+        cap = max(n - 1, 1)
+        if device:
+            import torch
+            dev = torch.device("cuda", int(self.info()["device"]))
+            d_core = self._mst_core(core, dev)
+            need = c_uint64(0)
+            _check(lib.ptk_mst_within_self_workspace(self._h, byref(need)))
+            ws = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
+            raw = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+            lab = torch.empty((n,), dtype=torch.int32, device=dev) if labels else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.ptk_mst_within_self_device(self._h, r, d_core.data_ptr() if d_core is not None else None,
+                                                  raw.data_ptr(), lab.data_ptr() if labels else None, ws.data_ptr(),
+                                                  need, byref(count), byref(rounds), stream))
+            self.last_mst_rounds = int(rounds.value)
+            raw = raw[:int(count.value)]
+            # (the _device form writes the set in no order: three stable sorts give (bits(w), lo, hi) ascending)
+            for col in (1, 0, 2):
+                raw = raw[torch.argsort(raw[:, col], stable=True)]
+            edges = (raw[:, 0].contiguous(), raw[:, 1].contiguous(), raw[:, 2].contiguous().view(torch.float32))
+            return (edges, lab) if labels else edges
+        host = self._mst_core(core, None)
+        edges = np.zeros((cap,), dtype=MST_EDGE)
+        lab = np.empty((n,), dtype=np.int32) if labels else None
+        cp = host.ctypes.data if host is not None else None
+        lp = lab.ctypes.data if labels else None
+        self._served(lib.ptk_mst_within_self(self._h, r, cp, edges.ctypes.data, byref(count), lp, byref(rounds)),
+                     lambda lib: lib.ptk_host_mst_within_self(self._h, self._pts.ctypes.data, r, cp, edges.ctypes.data,
+                                                              byref(count), lp))
+        self.last_mst_rounds = int(rounds.value)
+        edges = edges[:int(count.value)].copy()
+        return (edges, lab) if labels else edges
 
     def _host_radii(self, radii, nq: int):
         """The per-row radii of a host batch: any 1-D array-like of nq values, as a contiguous array of the tree's dtype."""

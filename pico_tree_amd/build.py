@@ -32,7 +32,7 @@ OBJ = os.path.join(CSRC, "_obj")
 #: the translation units of the library, the longest to compile first
 UNITS = ["ptk_family_knn", "ptk_backend", "ptk_family_nd", "ptk_family_radius", "ptk_family_f64", "ptk_family_self",
          "ptk_family_topo", "ptk_family_count", "ptk_family_align", "ptk_family_suppress",
-         "ptk_family_spacing"]
+         "ptk_family_spacing", "ptk_family_mst"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 
 #: -ffp-contract=off: the results contract forbids fused multiply-add

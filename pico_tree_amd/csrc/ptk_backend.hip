@@ -300,6 +300,7 @@ struct ProcessWarmup {
       ptkf::warm_self();
       ptkf::warm_align();
       ptkf::warm_suppress();
+      ptkf::warm_mst();
       ptkf::warm_spacing();
       (void)hipDeviceSynchronize();
       (void)hipGetLastError();
@@ -2619,6 +2620,97 @@ int ptk_suppress_within_self(const ptk_tree* t, float radius, const float* radii
   });
   if (rc == PTK_OK && n_kept != nullptr) *n_kept = count_kept(keep, t->n_points);
   return rc;
+}
+
+// ---- mst_within_self (ptk.h; the rounds: ptk_kernels_mst.hpp) ------------------------------------------------
+
+int ptk_mst_within_self_workspace(const ptk_tree* t, uint64_t* bytes) {
+  if (t == nullptr || bytes == nullptr) return fail(PTK_ERR_INVALID, "null argument");
+  *bytes = ptkf::mst_layout(t->n_points, ptkf::mst_branches(t)).bytes;
+  return PTK_OK;
+}
+
+// Enqueues Boruvka ROUNDS on `stream` until one adds no edge (or the forest is a tree): per round the component table,
+// the search over all pieces of leaf positions, the tie, emit and relabel passes.  As suppress_within_self it WAITS on
+// the stream once per round and reads 4 bytes (a stream under capture is refused), with the counter of that call's
+// pool.  The radius capture is neither read nor invalidated; the count side table is built on first use; everything
+// else lives in the caller's workspace.  Test hook mst_skip: 0 = no component table, 1 = the root and the far children
+// tested against it, 2 (the default: DESIGN.md section 8 has the measurement) = every near child too.
+int ptk_mst_within_self_device(const ptk_tree* t, float radius, const float* d_core, ptk_mst_edge* d_edges, int32_t* d_labels,
+                               void* d_workspace, uint64_t workspace_bytes, uint64_t* n_edges, uint32_t* n_rounds,
+                               void* stream) {
+  if (n_edges != nullptr) *n_edges = 0;
+  if (n_rounds != nullptr) *n_rounds = 0;
+  int rc = check_mst_self(t, radius, d_edges);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  const ptkf::MstLayout at = ptkf::mst_layout(t->n_points, ptkf::mst_branches(t));
+  if (d_workspace == nullptr) return fail(PTK_ERR_INVALID, "mst_within_self: null workspace");
+  if (workspace_bytes < at.bytes)
+    return fail(PTK_ERR_INVALID, "mst_within_self: the workspace holds %llu bytes, %llu points need %llu (ptk_mst_within_self_workspace)",
+                (unsigned long long)workspace_bytes, (unsigned long long)t->n_points, (unsigned long long)at.bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  rc = ptkf::suppress_check_stream(s);
+  if (rc != PTK_OK) return rc;
+  rc = count_table_of(t, s);
+  if (rc != PTK_OK) return rc;
+  char* ws = static_cast<char*>(d_workspace);
+  const uint32_t skip = (uint32_t)std::max(0, std::min(2, knob_int("mst_skip", 2)));
+  rc = ptkf::mst_begin(t, ws, s);
+  if (rc != PTK_OK) return rc;
+  rc = ptkf::mst_rounds(t->n_points, s, n_edges, n_rounds, [&](uint32_t* d_added, uint32_t rounds_before) {
+    int r = PTK_OK;
+    if (rounds_before > 0 && skip != 0u) r = ptkf::mst_table(t, ws, s);
+    if (r == PTK_OK)
+      r = in_batch_pieces(t->n_points, [&](uint64_t first, uint64_t n) {
+        return ptkf::mst_search(t, first, n, radius, d_core, ws, skip, rounds_before > 0, s);
+      });
+    if (r == PTK_OK) r = ptkf::mst_join(t, ws, d_edges, d_added, s);
+    return r;
+  });
+  if (rc == PTK_OK && d_labels != nullptr)
+    PTK_HIP(hipMemcpyAsync(d_labels, ws + at.label, (size_t)t->n_points * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  return rc;
+}
+
+// The host form: one block per call holds core, the edges, the labels and the workspace; core goes up, the edges come
+// down and are sorted into the order of the contract, the labels come down.
+int ptk_mst_within_self(const ptk_tree* t, float radius, const float* core, ptk_mst_edge* edges, uint64_t* n_edges,
+                        int32_t* labels, uint32_t* n_rounds) {
+  if (n_edges != nullptr) *n_edges = 0;
+  if (n_rounds != nullptr) *n_rounds = 0;
+  int rc = check_mst_self(t, radius, edges);
+  if (rc == PTK_OK && t != nullptr) rc = check_core(core, t->n_points);
+  if (rc != PTK_OK || t->n_points == 0) return rc;
+  DeviceGuard guard(t->device);
+  if (!guard.ok) return fail(PTK_ERR_DEVICE, "hipSetDevice(%d) failed", t->device);
+  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t n = (size_t)t->n_points;
+  const size_t o_edges = pad(n * sizeof(float)), o_labels = o_edges + pad(n * sizeof(ptk_mst_edge));
+  const size_t o_ws = o_labels + pad(n * sizeof(int32_t));
+  const size_t ws_bytes = ptkf::mst_layout(t->n_points, ptkf::mst_branches(t)).bytes;
+  DeviceBlock block;
+  if (block.alloc(o_ws + ws_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(PTK_ERR_NOMEM, "out of device memory (the edges and the workspace of mst_within_self)");
+  }
+  char* base = block.as<char>();
+  if (core != nullptr) PTK_HIP(hipMemcpy(base, core, n * sizeof(float), hipMemcpyHostToDevice));
+  uint64_t count = 0;
+  rc = ptk_mst_within_self_device(t, radius, core != nullptr ? reinterpret_cast<const float*>(base) : nullptr,
+                                  reinterpret_cast<ptk_mst_edge*>(base + o_edges), reinterpret_cast<int32_t*>(base + o_labels),
+                                  base + o_ws, ws_bytes, &count, n_rounds, nullptr);
+  // (the block is freed when this returns: everything enqueued on it has to be done -- also after a refusal half-way)
+  hipError_t he = hipStreamSynchronize(nullptr);
+  if (rc != PTK_OK) return rc;
+  if (he == hipSuccess && count > 0) he = hipMemcpy(edges, base + o_edges, (size_t)count * sizeof(ptk_mst_edge), hipMemcpyDeviceToHost);
+  if (he == hipSuccess && labels != nullptr) he = hipMemcpy(labels, base + o_labels, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (he != hipSuccess) return fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
+  static_assert(sizeof(ptk_mst_edge) == sizeof(pico_tree::internal::mst_edge), "record layout");
+  pico_tree::internal::mst_sort(reinterpret_cast<pico_tree::internal::mst_edge*>(edges), (size_t)count);
+  if (n_edges != nullptr) *n_edges = count;
+  return PTK_OK;
 }
 
 // ---- normals_within_self (ptk.h; the kernel: ptk_kernels_frames.hpp) ----------------------------------------

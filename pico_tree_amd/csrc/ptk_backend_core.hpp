@@ -65,6 +65,7 @@ constexpr int kGenLeafB = 5;  // points per leaf round of the general searches (
 
 // Host-side builder: the product's own header-only flat-tree builder.
 #include "pico_tree/internal/flat_tree.hpp"
+#include "pico_tree/internal/mst.hpp"
 #include "pico_tree/internal/stream.hpp"
 #include "pico_tree/internal/suppress.hpp"
 #include "pico_tree/map.hpp"
@@ -773,6 +774,40 @@ inline int check_radius_self(const Tree* t, double radius, const Real* radii, bo
   if (deep_stack_class(t))
     return fail(PTK_ERR_UNSUPPORTED, "%s: tree depth %u runs on the host loop only (%s)", what, t->max_depth, host_loop);
   return PTK_OK;
+}
+
+// mst_within_self (ptk.h): a scalar radius only.  The search prunes by box distances, so the device serves the metrics
+// whose box distance is a lower bound of the point distance: metric_l2_squared and metric_l1, on
+// the handles count_within_self serves.  Every other handle is refused with the reason and the host loop.
+inline bool mst_metric(const ptk_tree* t) {
+  const int m = t->metric.load();
+  return m == PTK_METRIC_L2_SQUARED || m == PTK_METRIC_L1;
+}
+inline int check_mst_self(const ptk_tree* t, float radius, const void* edges) {
+  if (t == nullptr) return fail(PTK_ERR_INVALID, "null tree");
+  int rc = check_search(t, t, t->n_points);
+  if (rc == PTK_OK) rc = check_radius(radius);
+  if (rc != PTK_OK) return rc;
+  if (edges == nullptr && t->n_points > 1) return fail(PTK_ERR_INVALID, "null edge buffer");
+  const char* host_loop = "ptk_host_mst_within_self";
+  if (topological(t))
+    return fail(PTK_ERR_UNSUPPORTED, "mst_within_self: topological metrics are not served (%s serves metric_l2_squared and metric_l1)",
+                host_loop);
+  if (!mst_metric(t))
+    return fail(PTK_ERR_UNSUPPORTED,
+                "mst_within_self: metric_lpinf and metric_lninf are not served: the box distance is no lower bound of the "
+                "weight order there (%s serves metric_l2_squared and metric_l1)",
+                host_loop);
+  if (t->dim > 3) return fail(PTK_ERR_UNSUPPORTED, "mst_within_self: dim > 3 runs on the host loop only (%s)", host_loop);
+  if (deep_stack_class(t))
+    return fail(PTK_ERR_UNSUPPORTED, "mst_within_self: tree depth %u runs on the host loop only (%s)", t->max_depth, host_loop);
+  return PTK_OK;
+}
+// The core distances of the host forms (null: none): the first NaN or negative entry is refused by its row.
+inline int check_core(const float* core, uint64_t n) {
+  if (core == nullptr) return PTK_OK;
+  const uint64_t i = pico_tree::internal::mst_first_bad_core(core, n);
+  return i == n ? PTK_OK : fail(PTK_ERR_INVALID, "core[%llu] must be >= 0 (and not NaN)", (unsigned long long)i);
 }
 
 // normals_within_self (ptk.h): a normal is defined for Euclidean 3-D points -- dim != 3 and the topological metrics are

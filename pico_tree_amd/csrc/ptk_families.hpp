@@ -327,6 +327,58 @@ inline int spacing_host_form(uint64_t n, Real* mean, Real* kth, uint8_t* keep, p
   if (he != hipSuccess) return ptkb::fail(PTK_ERR_DEVICE, "HIP error: %s", hipGetErrorString(he));
   return PTK_OK;
 }
+// ptk_family_mst.hip: mst_within_self (ptk_kernels_mst.hpp).  The caller's workspace: a 256-byte
+// header whose first word is the number of edge records, then the arrays of the kernel header, each 256-byte aligned.
+struct MstLayout {
+  size_t parent, label, cand, best_wlo, best_hi, comp, info, arrive, bytes;
+};
+// The branches the component table covers: none for a tree whose root is a leaf (the encoder keeps one padding record).
+inline uint64_t mst_branches(const ptk_tree* t) { return (t->dev.root_ref & 0x80000000u) != 0 ? 0 : t->n_branches; }
+inline MstLayout mst_layout(uint64_t n, uint64_t n_branches) {
+  const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  MstLayout at;
+  at.parent = 256;
+  at.label = at.parent + pad((size_t)n * 4);
+  at.cand = at.label + pad((size_t)n * 4);
+  at.best_wlo = at.cand + pad((size_t)n * 8);
+  at.best_hi = at.best_wlo + pad((size_t)n * 8);
+  at.comp = at.best_hi + pad((size_t)n * 4);
+  at.info = at.comp + pad((size_t)n_branches * 4);
+  at.arrive = at.info + pad((size_t)n_branches * 4);
+  at.bytes = at.arrive + pad((size_t)n_branches * 4);
+  return at;
+}
+// mst_begin: the arrays at their start (every point a component), the branches' parent links.  A round: mst_table (not
+// before the first round, and not with skip == 0), mst_search over all pieces of leaf positions, mst_join (the tie pass,
+// the emit-and-link pass -- it adds the edges it writes to *d_added --, the relabel pass).
+int mst_begin(const ptk_tree* t, char* ws, hipStream_t s);
+int mst_table(const ptk_tree* t, char* ws, hipStream_t s);
+int mst_search(const ptk_tree* t, uint64_t first, uint64_t n, float radius, const float* d_core, char* ws, uint32_t skip,
+               bool later_round, hipStream_t s);
+int mst_join(const ptk_tree* t, char* ws, ptk_mst_edge* d_edges, uint32_t* d_added, hipStream_t s);
+void warm_mst();
+// The rounds: `round(d_added, rounds_before)` enqueues one.  The counter is suppress_within_self's (its pool, its wait);
+// the call ends when a round adds nothing, or when the forest is a tree.  *n_edges, *n_rounds: may be null.
+template <class Round>
+inline int mst_rounds(uint64_t n_points, hipStream_t s, uint64_t* n_edges, uint32_t* n_rounds, Round&& round) {
+  SuppressCounter counter;
+  int rc = counter.alloc();
+  uint32_t rounds = 0, added = 1;
+  uint64_t total = 0;
+  // (every round that adds an edge joins two components: at most n_points - 1 of them, and one that adds nothing)
+  while (rc == PTK_OK && added != 0 && total + 1 < n_points && rounds < n_points) {
+    rc = counter.zero(s);
+    if (rc == PTK_OK) rc = round(counter.d_word, rounds);
+    if (rc == PTK_OK) rc = counter.read(s, &added);
+    total += added;
+    ++rounds;
+  }
+  if (n_rounds != nullptr) *n_rounds = rounds;
+  if (n_edges != nullptr) *n_edges = rc == PTK_OK ? total : 0;
+  // (after a failure half-way: nothing of this call is left running on the counter when it goes back to the pool)
+  if (rc != PTK_OK) (void)hipStreamSynchronize(s);
+  return rc;
+}
 // Rows of a piece of the staged route: its two temporaries (the query rows, the k + 1 records per row) stay under
 // kSelfStageBytes; test hook self_piece.
 constexpr size_t kSelfStageBytes = size_t(256) << 20;

@@ -705,6 +705,37 @@ int ptk_host_suppress_within_self(const ptk_tree* t, const float* points, float 
   return PTK_OK;
 }
 
+// mst_within_self (ptk.h) as the contract reads: the rows of the self loop above, the edges sorted by (bits(w), lo, hi),
+// Kruskal with a union-find (pico_tree/internal/mst.hpp).  Every float32 handle under metric_l2_squared and metric_l1.
+int ptk_host_mst_within_self(const ptk_tree* t, const float* points, float radius, const float* core, ptk_mst_edge* edges,
+                             uint64_t* n_edges, int32_t* labels) {
+  if (n_edges != nullptr) *n_edges = 0;
+  int rc = ptk_host::check_host_self(t, points, radius, nullptr);
+  if (rc == PTK_OK) rc = check_core(core, t->n_points);
+  if (rc != PTK_OK) return rc;
+  if (!mst_metric(t))
+    return fail(PTK_ERR_UNSUPPORTED, "mst_within_self: the host loop serves metric_l2_squared and metric_l1 only");
+  if (edges == nullptr && t->n_points > 1) return fail(PTK_ERR_INVALID, "null edge buffer");
+  static_assert(sizeof(ptk_mst_edge) == sizeof(pico_tree::internal::mst_edge), "record layout");
+  try {
+    using namespace ptk_host;
+    const std::shared_ptr<const flat_t> flat_holder = flat_of(t);
+    const flat_t& flat = *flat_holder;
+    space_t space(points, t->n_points, t->dim);
+    view_t view(space);
+    std::vector<std::vector<neighbor_t>> per_row(t->n_points);
+    radius_self_rows(t, flat, view, points, 0, per_row, [&](uint64_t) { return radius; });
+    const uint64_t count =
+        internal::mst_rows(per_row, radius, core, reinterpret_cast<pico_tree::internal::mst_edge*>(edges), labels);
+    if (n_edges != nullptr) *n_edges = count;
+  } catch (const std::bad_alloc&) {
+    return fail(PTK_ERR_NOMEM, "out of host memory");
+  } catch (const std::exception& ex) {
+    return fail(PTK_ERR_INVALID, "host search failed: %s", ex.what());
+  }
+  return PTK_OK;
+}
+
 int ptk_host_search_box(const ptk_tree* t, const float* points, const float* mins, const float* maxs, uint64_t nb,
                         uint64_t* offsets, int32_t** out) {
   if (t == nullptr || points == nullptr || offsets == nullptr || out == nullptr || (nb > 0 && (mins == nullptr || maxs == nullptr)))
